@@ -12,12 +12,14 @@ cost (lc_key_cost), and each rank checks its own range: total work is fixed
 data path has no collective; the only cross-rank traffic is the timing
 barrier/max and the gather of per-rank ranges and times (RCCL).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with the
-roofline of the dominant kernel (fast_tier_kernel on C2; HIP events on its
-stream) and a CPU baseline: the oracle's C restatement of knossos (faster of
-its JIT and WGL analyzers) on a bounded sample of the same workload, on host
-threads.  Outside the timed region, rank 0 also decides BASELINE configs[3]
-(one hot key, 5k ops, concurrency 50, 20 % :info) and reports its time.
+Prints ONE JSON line on rank 0, with the roofline of the dominant kernel
+(fast_tier_kernel on C2; HIP events on its stream, recorded within the timed
+steps).  A plain run does no more: set-up, warm-up, the timed steps, the
+result files of --dump-outputs, the line.  With --full, outside the timed
+region, it also runs every secondary leg — among them BASELINE configs[3]
+(one hot key, 5k ops, concurrency 50, 20 % :info) — and a CPU baseline: the
+oracle's C restatement of knossos (faster of its JIT and WGL analyzers) on a
+bounded sample of the same workload, on host threads.
 """
 import argparse
 import json
@@ -55,16 +57,25 @@ def parse():
     ap.add_argument("--cpu-sample-keys", type=int, default=10000)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every secondary leg "
+                         "(other configurations, host-buffer and multi-GPU "
+                         "paths, oracle comparisons) and the CPU baseline")
     ap.add_argument("--bare", action="store_true",
-                    help="timed region only (no CPU baseline, no hot-key leg): "
-                         "for rocprofv3 runs whose per-kernel averages must "
-                         "match the bench line")
+                    help="timed region only, whatever --full says (the default "
+                         "since --full exists): for rocprofv3 runs whose "
+                         "per-kernel averages must match the bench line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's results "
+                         "(one float64 array per lc_result field, one row per "
+                         "key) as DIR/<field>.npy")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r06", "traffic_fast_tier.json"))
     return ap.parse_args()
 
 
 def main():
     args = parse()
+    full = args.full and not args.bare
     # stdout carries only the JSON line: everything else written to fd 1 —
     # RCCL's version banner, gloo's "Rank r is connected to n peer ranks"
     # whenever a gloo group forms, the library's RCCL communicators — goes to
@@ -155,6 +166,8 @@ def main():
     hms, jms, gms = [last["hbm_kernel_ms"]], [last["jit_kernel_ms"]], [last["gap_kernel_ms"]]
     njit = [last["n_jit_keys"]]
     res = np.frombuffer(d_out.cpu().numpy().tobytes(), dtype=abi.RESULT_DTYPE)[:my_keys]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
     ranks = (D.gather_rows([rank, ka, kb, n_ops, own * 1e3 / args.steps,
                             float(np.mean(kms))])
              if distributed else
@@ -164,12 +177,12 @@ def main():
     after_barrier = reduce_run(after_barrier, 0, res, distributed, dev)[0]
     # every rank together, outside the timed region: the one collective path
     fx_ranks = (oversized_key_ranks(abi, world, local)
-                if distributed and world > 1 and not args.bare else None)
+                if distributed and world > 1 and full else None)
     # rank 0 alone, the other ranks parked on a CPU (gloo) barrier so no
     # spinning collective kernel shares their GPUs: the drop-in's own
     # multi-GPU path — one lc_ctx over all N GPUs, lc_check from host memory
     fanout = None
-    if not args.bare:
+    if full:
         park = None
         if distributed:
             import datetime
@@ -263,7 +276,7 @@ def main():
         line["oversized_key_ranks"] = fx_ranks
     if fanout is not None:
         line["fanout_leg"] = fanout
-    if rank == 0 and not args.bare:
+    if rank == 0 and full:
         if world == 1:  # first, in the timed loop's own state (no leg has run on the context yet)
             line["c3_shards"] = c3_shards(ctx, abi, ops, key_off, d_ops, d_off, dev, stream)
             line["resident32_leg"] = resident32_leg(ctx, abi, ops, key_off, d_ops, d_off, dev, stream)
@@ -279,7 +292,7 @@ def main():
         line["crash_leg"] = crash_leg(ctx, abi, dev, stream)
         line["oversized_key"] = oversized_key(ctx, abi)
 
-    if rank == 0 and world == 1 and not (args.no_cpu_baseline or args.bare):
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args, ops, key_off, res)
 
     if rank == 0:
@@ -301,6 +314,28 @@ def bind_steps(ctx, abi, d_ops, d_off, n_keys, d_out, stream):
     return [ctx.bind_check_device(d_ops, d_off, n_keys, d_out, stream=stream,
                                   opts=abi.default_opts(flags=f))
             for f in (0, abi.LC_FLAG_NO_TIMING)]
+
+
+DUMP_MAX_KEYS = 1 << 20   # 6 float64 fields per key: 48 MB
+
+
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: what the last timed step left in the caller's result
+    buffer — this rank's lc_result records, one per key of its range — as one
+    float64 array per field (verdict.npy, reason.npy, fail_op.npy, ...; 480 kB
+    in all for C2).  The fields are integers, which float64 holds exactly
+    below 2^53.  The batch is seeded, so two builds run with the same
+    arguments can be compared file for file.  Under torchrun with N > 1 ranks
+    every rank writes its own key range as <field>.rank<r>.npy.  Above
+    DUMP_MAX_KEYS keys a fixed, seeded sample of that many keys is written,
+    in key order, which keeps the files under 64 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    if len(res) > DUMP_MAX_KEYS:
+        res = res[np.sort(np.random.RandomState(0x5EED).choice(len(res), DUMP_MAX_KEYS,
+                                                                replace=False))]
+    suffix = ".rank%d" % rank if world > 1 else ""
+    for f in res.dtype.names:
+        np.save(os.path.join(path, f + suffix + ".npy"), res[f].astype(np.float64))
 
 
 def c3_shards(ctx, abi, ops, key_off, d_ops, d_off, dev, stream, steps=200, warmup=20):

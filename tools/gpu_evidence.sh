@@ -43,5 +43,5 @@ python tools/pmc_traffic.py $O/prof $O/ptraffic r05 10000000 > $O/traffic.log 2>
 GRAFT_REPO_ROOT=$R bash tools/fused_pmc.sh > $O/fused_pmc.txt 2>&1 || { tail -5 $O/fused_pmc.txt; exit 1; }
 GRAFT_REPO_ROOT=$R bash tools/gap_pmc.sh hot hot > $O/gap_pmc.txt 2>&1 || { tail -5 $O/gap_pmc.txt; exit 1; }
 echo "pmc done"
-timeout -k 10 900 python bench.py --traffic-json $O/ptraffic/traffic_r05.json > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full --traffic-json $O/ptraffic/traffic_r05.json > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python -c "import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print('value %.4g ms %.4f frac %.3f traffic %s' % (d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['traffic']))"

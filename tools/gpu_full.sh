@@ -1,16 +1,20 @@
 #!/bin/bash
 # the round-end checks: every GPU test, smoke, then the full bench line
+# (bench.py --full: the timed steps, every secondary leg, the CPU baseline).
+# Logs and the line go to $OUT_DIR (default build/out).
 set -o pipefail
-mkdir -p gpurun_out
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu_full.log 2>&1
-rc=$?; tail -3 gpurun_out/pytest_gpu_full.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
-rc=$?; tail -2 gpurun_out/smoke.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py > gpurun_out/bench_full.json 2> gpurun_out/bench_full.err
-rc=$?; [ $rc -eq 0 ] || { tail -5 gpurun_out/bench_full.err; exit $rc; }
+export O=${OUT_DIR:-build/out}
+mkdir -p $O
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest_gpu_full.log 2>&1
+rc=$?; tail -3 $O/pytest_gpu_full.log; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
+rc=$?; tail -2 $O/smoke.log; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 600 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err
+rc=$?; [ $rc -eq 0 ] || { tail -5 $O/bench_full.err; exit $rc; }
 python - <<'PY'
 import json
-d = json.load(open("gpurun_out/bench_full.json"))
+import os
+d = json.load(open(os.path.join(os.environ["O"], "bench_full.json")))
 print("value %.4g ms/step %.4f frac %.3f" % (d["value"], d["ms_per_step"], d["roofline"]["frac"]))
 print("crash_leg", {k: d["crash_leg"][k] for k in ("call_ms", "fast_kernel_ms", "gap_kernel_ms")})
 print("hot_key", d["hot_key"])
