@@ -96,39 +96,45 @@ constexpr int64_t kGapWaveMinKeys = 1024;             // ... when there are more
 constexpr int64_t kGapWideMaxKeys = 64;    // at most this many keys for the gap tier ...
 constexpr int kGapWideMinLen = 2048;        // ... the longest of them this long: 512-thread workgroups
 
+// A device buffer with its capacity in bytes (ensure(): at least 256 bytes,
+// grow-only, freed at lc_close).  No destructor: lc_open copies a Dev into
+// lc_ctx::devs, and lc_close frees every buffer once.
+template <class T>
+struct Buf {
+  T *p = nullptr;
+  size_t cap = 0;
+};
+
 struct Dev {
   int id = -1;
   hipStream_t stream = nullptr;
+
+  // ---- device buffers (each is named once more, in lc_close's list) ----
+  Buf<lc_op> d_ops;
+  Buf<int64_t> d_off;
+  Buf<lc_key_result> d_out;
+  Buf<int32_t> d_ovf, d_ovf2;
+  Buf<int32_t> d_jit;
+  Buf<int32_t> d_flags;         // per key: handed over by the fast tier (zero between calls)
+  Buf<int32_t> d_jit2;          // keys the gap tier passes on
+  Buf<int32_t> d_gap2;          // keys the crash-light pass leaves to the gap tier
+  Buf<int32_t> d_gws;           // gap-tier workspace
+  Buf<char> d_cex;              // gap-tier counterexample intervals + probes
+  Buf<void> d_ws;               // HBM tiers' workspace
+  Buf<int32_t> d_wit, d_kind;   // lc_check_ex: device copies of the lc_aux outputs
+  Buf<int32_t> d_cert, d_cset;  // lc_aux certificates (4 per key), their position sets
+  Buf<int32_t> d_cws;           // certificate workspace
+  Buf<char> d_ops32;            // copy pipeline: lc_check32 / lc_check16's staging records
+  Buf<int64_t> d_base;          // ... and the keys' bases
+
+  // ---- events ----
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-  void *d_ops = nullptr;
-  size_t ops_cap = 0;
-  int64_t *d_off = nullptr;
-  size_t off_cap = 0;
-  lc_key_result *d_out = nullptr;
-  size_t out_cap = 0;
-  int32_t *d_ovf = nullptr;
-  size_t ovf_cap = 0;
-  int32_t *d_ovf2 = nullptr;
-  size_t ovf2_cap = 0;
-  int32_t *d_jit = nullptr;
-  size_t jit_cap = 0;
-  int32_t *d_flags = nullptr;          // per key: handed over by the fast tier (zero between calls)
-  size_t flags_cap = 0;
-  int32_t *d_jit2 = nullptr;           // keys the gap tier passes on
-  size_t jit2_cap = 0;
-  int32_t *d_gap2 = nullptr;           // keys the crash-light pass leaves to the gap tier
-  size_t gap2_cap = 0;
-  hipEvent_t el = nullptr;             // after the crash-light pass
-  int32_t *d_gws = nullptr;            // gap-tier workspace
-  size_t gws_cap = 0;
-  char *d_cex = nullptr;               // gap-tier counterexample intervals + probes
-  size_t cex_cap = 0;
-  hipEvent_t eg = nullptr;
-  double gap_ms = 0;
-  int64_t n_gap = 0;
-  hipEvent_t ef = nullptr;
-  double fast_ms = 0, jit_ms = 0;
-  int64_t n_jit = 0;
+  hipEvent_t ef = nullptr;                  // after the first pass
+  hipEvent_t el = nullptr;                  // after the crash-light pass
+  hipEvent_t eg = nullptr;                  // after the gap tier
+  hipEvent_t eh0 = nullptr, eh1 = nullptr;  // around lc_check's host-to-device copies
+
+  // ---- status words, and what the next call has to know about them ----
   lcdev::KStatus *d_status = nullptr;   // all-zero between calls
   lcdev::KStatus *h_status = nullptr;   // pinned: D2H copies of d_status
   int32_t *h_handoff = nullptr;         // host-coherent: [0] fast tier handed keys over, [1] a fused
@@ -144,40 +150,13 @@ struct Dev {
   hipEvent_t es = nullptr;
   bool st_pending = false;
   int64_t st_keys = 0;
-  void *d_ws = nullptr;
-  size_t ws_cap = 0;
-  int32_t *d_wit = nullptr;            // lc_check_ex: device copies of the lc_aux outputs
-  size_t wit_cap = 0;
-  int32_t *d_kind = nullptr;
-  size_t kind_cap = 0;
-  int32_t *d_cert = nullptr;           // lc_aux certificates (4 per key), their position sets
-  size_t cert_cap = 0;
-  int32_t *d_cset = nullptr;
-  size_t cset_cap = 0;
-  int32_t *d_cws = nullptr;            // certificate workspace
-  size_t cws_cap = 0;
-  double kernel_ms = 0, hbm_ms = 0;
-  int64_t n_hbm = 0;
-  int malformed = 0;
   bool use_fused = false;  // the next call takes the fused version-order + crash-light pass
-  hipEvent_t eh0 = nullptr, eh1 = nullptr;  // around lc_check's host-to-device copies
-  lc_device_stats last{};                   // this device's share of the last lc_check
-  // lc_check's host-to-device pipeline: the copy stream, one event per chunk
-  // (its records landed), the 24-byte staging records of lc_check32 /
-  // lc_check_device32 and the keys' bases
-  // (two copy streams, chunks alternating: two DMA engines read host memory
-  // at once; measured 52-53 GB/s with one, 57 GB/s with two on one GPU)
-  hipStream_t cst = nullptr, cst2 = nullptr;
-  std::vector<hipEvent_t> cev;
-  void *d_ops32 = nullptr;
-  size_t ops32_cap = 0;
-  int64_t *d_base = nullptr;
-  size_t base_cap = 0;
   // some key of the last run_device call may be LC_INVALID (a key was handed
   // over past the version-order tier, which decides valid keys only): the
   // certificate pass runs only then
   bool maybe_invalid = true;
-  double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
+
+  // ---- completion signal ----
   // The version-order / fused pass's follower signal (kernels.h
   // launch_done_signal): a host-mapped word the host spins on instead of
   // waiting for an event; the pass's HIP-event time is read later
@@ -185,6 +164,8 @@ struct Dev {
   uint32_t *h_done = nullptr, *h_done_dev = nullptr;
   uint32_t seq = 0;
   bool timing_pending = false;
+
+  // ---- resident grid ----
   // the resident version-order grid (kernels.h launch_fast_resident), on its
   // own stream; res_grid: workgroups of the live grid (0: none)
   lcdev::ResHost *res_h = nullptr, *res_h_dev = nullptr;
@@ -196,14 +177,28 @@ struct Dev {
   int64_t res_idle_us = 50; // LC_RESIDENT_IDLE_US (read at each grid launch)
   int64_t res_cap = -1;     // lcdev::fast_resident_capacity() (once)
   bool res_broken = false;  // a request the grid did not complete: launches only from then on
+
+  // ---- copy pipeline ----
+  // lc_check's host-to-device pipeline: the copy streams and one event per
+  // chunk (its records landed); the staging records are d_ops32 / d_base
+  // (two copy streams, chunks alternating: two DMA engines read host memory
+  // at once; measured 52-53 GB/s with one, 57 GB/s with two on one GPU)
+  hipStream_t cst = nullptr, cst2 = nullptr;
+  std::vector<hipEvent_t> cev;
+  // lc_check's small calls from pageable memory: inputs and outputs pass
+  // through this pinned buffer (kStageMax)
+  char *h_stage = nullptr;
+
+  // ---- statistics ----
+  double kernel_ms = 0, fast_ms = 0, gap_ms = 0, jit_ms = 0, hbm_ms = 0;
+  int64_t n_gap = 0, n_jit = 0, n_hbm = 0;
+  int malformed = 0;
+  lc_device_stats last{};                   // this device's share of the last lc_check
+  double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
   // this device's share of lc_last_totals: written only by the device's own
   // thread during a call (check_host runs one per device), summed by
   // lc_last_totals after the threads are joined
   lc_totals tot{};
-  // lc_check's small calls from pageable memory: inputs and outputs pass
-  // through this pinned buffer (kStageMax)
-  char *h_stage = nullptr;
-  size_t stage_cap = 0;
 };
 
 }  // namespace
@@ -241,19 +236,25 @@ void set_err(lc_ctx *c, const std::string &s) {
   } while (0)
 
 template <class T>
-int ensure(lc_ctx *c, T **p, size_t *cap, size_t need) {
-  if (*cap >= need && *p) return 0;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  size_t n = std::max<size_t>(need, 256);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(p), n);
+int ensure(lc_ctx *c, Buf<T> &b, size_t bytes) {
+  if (b.cap >= bytes && b.p) return 0;
+  if (b.p) (void)hipFree(b.p);
+  b = Buf<T>{};
+  const size_t n = std::max<size_t>(bytes, 256);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.p), n);
   if (e != hipSuccess) {
+    b.p = nullptr;
     set_err(c, std::string("hipMalloc: ") + hipGetErrorString(e));
     return -ENOMEM;
   }
-  *cap = n;
+  b.cap = n;
   return 0;
+}
+
+// NAME=0 in the environment: a path's switch, read where the path is chosen
+bool env_is_off(const char *name) {
+  const char *e = getenv(name);
+  return e && e[0] == '0';
 }
 
 int opts_to_params(lc_ctx *c, const lc_opts *o, lcdev::KParams *p) {
@@ -322,12 +323,8 @@ constexpr int kMaxChunks = 48;
 // microseconds per copy, which small calls (C1, C4) pay in full.  At a few
 // MB the runtime's path is the faster one again (a 4.8 MB input staged:
 // 0.07-0.15 ms slower, profiles/r05/stage_ab.txt).
-// LC_STAGE=0 (A/B): the pageable copies.
 constexpr size_t kStageMax = size_t(2) << 20;
-bool stage_off() {
-  const char *e = getenv("LC_STAGE");
-  return e && e[0] == '0';
-}
+inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 // The device's staging buffer (kStageMax bytes, allocated on first use), or
 // null with the context's error set.
 char *stage_buf(lc_ctx *c, Dev &d) {
@@ -337,27 +334,31 @@ char *stage_buf(lc_ctx *c, Dev &d) {
       set_err(c, "hipHostMalloc (staging) failed");
       return nullptr;
     }
-    d.stage_cap = kStageMax;
   }
   return d.h_stage;
 }
 
 // Device-side lc_aux outputs of one run_device call (null: not wanted).
-struct WitOut {
+struct AuxOut {
   int32_t *wit = nullptr;   // per record, indexed like d_ops
   int32_t *kind = nullptr;  // per key
   int32_t *cert = nullptr;  // per key, 4 int32 (infeasibility certificates)
   int32_t *cset = nullptr;  // per record (HALL position sets)
   int64_t n_records = 0;
-  // (not an output) the shard's key offsets in host memory when the caller
-  // has them (lc_check_ex): the gap tier may then be launched early
+};
+
+// Where a run_device call's records come from, beyond d_ops / d_off
+// (default: 48-byte records in place, offsets on the device only).
+struct Source {
+  // the shard's key offsets in host memory when the caller has them
+  // (lc_check_ex): the gap tier may then be launched early
   const int64_t *h_off = nullptr;
-  // (not an output) lc_check's chunked copies, or null: the records are in place
+  // lc_check's chunked copies, or null: the records are in place
   const Chunks *chunks = nullptr;
-  // (not an output) the first pass over lc_op32 records (lc_check32 /
-  // lc_check_device32 without lc_aux outputs): ops32 and the keys' bases
-  // (null: 0), indexed like d_ops / d_off; `widen` fills the 48-byte records
-  // the later tiers read (and names them) once a key is handed over
+  // the first pass over lc_op32 records (lc_check32 / lc_check_device32
+  // without lc_aux outputs): ops32 and the keys' bases (null: 0), indexed
+  // like d_ops / d_off; `widen` fills the 48-byte records the later tiers
+  // read (and names them) once a key is handed over
   const lc_op32 *ops32 = nullptr;
   const int64_t *base32 = nullptr;
   std::function<int(const lc_op **)> widen;
@@ -377,7 +378,7 @@ struct GapPlan {
 // (cert.hip), after every tier has decided.
 int run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
                      const lcdev::KParams &p, const lc_key_result *d_out, hipStream_t st,
-                     const WitOut &wo) {
+                     const AuxOut &wo) {
   if (!wo.cert || !wo.cset || n_keys <= 0) return 0;
   if (!d.maybe_invalid) {
     // every key was decided by the version-order tier, which decides valid
@@ -385,10 +386,8 @@ int run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off
     HIP_TRY(c, lcdev::launch_cert_none(wo.cert, n_keys, st));
     return 0;
   }
-  if (int rc = ensure(c, reinterpret_cast<char **>(&d.d_cws), &d.cws_cap,
-                      lcdev::cert_ws_bytes(wo.n_records, n_keys)))
-    return rc;
-  HIP_TRY(c, lcdev::launch_certificates(d_ops, d_off, n_keys, wo.n_records, p, d_out, d.d_cws,
+  if (int rc = ensure(c, d.d_cws, lcdev::cert_ws_bytes(wo.n_records, n_keys))) return rc;
+  HIP_TRY(c, lcdev::launch_certificates(d_ops, d_off, n_keys, wo.n_records, p, d_out, d.d_cws.p,
                                         wo.cert, wo.cset, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   return 0;
@@ -423,11 +422,11 @@ void settle_timing(lc_ctx *c, Dev &d) {
   }
 }
 
-// LC_NATIVE32=0 (A/B): 24-byte records are widened before the first pass, as
-// in the first ABI-4 build, instead of decided as they are
-bool native32_off() {
-  const char *e = getenv("LC_NATIVE32");
-  return e && e[0] == '0';
+// d_status copied into h_status, and waited for.
+int read_status(lc_ctx *c, Dev &d, hipStream_t st) {
+  HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return 0;
 }
 
 // Wait for the pass's follower signal (seq in *h_done): spin, checking the
@@ -461,10 +460,6 @@ int wait_done(lc_ctx *c, Dev &d, uint32_t seq, hipStream_t st) {
 // kernel.  The grid leaves after LC_RESIDENT_IDLE_US (default 50) without a
 // request, before any other work of this library runs on the device, and at
 // lc_close.  LC_RESIDENT=0 turns it off (every call launches).
-bool resident_off() {
-  const char *e = getenv("LC_RESIDENT");
-  return e && e[0] == '0';
-}
 
 // Write request number d.res_seq + 1 (every word tagged with it).
 void res_ring(Dev &d, const uint64_t (&v)[lcdev::kResWords]) {
@@ -507,7 +502,7 @@ int res_request(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int
   if (hipStreamQuery(st) != hipSuccess) HIP_TRY(c, hipStreamSynchronize(st));
   lcdev::ResHost *h = d.res_h;
   const uint64_t v[lcdev::kResWords] = {
-      (uint64_t)d_ops, (uint64_t)d_off, (uint64_t)n_keys, (uint64_t)d_out, (uint64_t)d.d_flags,
+      (uint64_t)d_ops, (uint64_t)d_off, (uint64_t)n_keys, (uint64_t)d_out, (uint64_t)d.d_flags.p,
       (uint64_t)d.d_status, (uint64_t)d.h_handoff_dev, (uint64_t)(uint32_t)p.init_ver,
       (uint64_t)(uint32_t)p.init_val};
   for (int attempt = 0; attempt < 3; attempt++) {
@@ -567,441 +562,502 @@ int res_request(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int
   return 1;
 }
 
-// Run the tiers for n_keys keys whose device arrays are in place.
-int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off,
-               int64_t n_keys, const lcdev::KParams &p,
-               lc_key_result *d_out, hipStream_t st, int64_t flags,
-               const WitOut &wo = WitOut()) {
+// One run_device call: its arguments, what follows from them, and what one
+// stage leaves for the next.  The stages below read and write this and Dev.
+struct Run {
+  lc_ctx *c;
+  Dev &d;
+  const lc_op *d_ops;  // (a native 24-byte pass: named by Source::widen at the handoff)
+  const int64_t *d_off;
+  int64_t n_keys;
+  const lcdev::KParams &p;
+  lc_key_result *d_out;
+  hipStream_t st;
+  int64_t flags;
+  const AuxOut &ao;
+  const Source &src;
+  bool fast_on = false;
+  // With the gap tier on, the fast tier sends keys it can only pass on (no
+  // version on an :ok mutation, a read [nil x], malformed) straight to the
+  // JIT list d_jit2, which the gap tier then appends to.
+  bool gap_on = false;
+  bool want_wit = false;
+  // A call with one pass launch (no chunks) returns on the pass's follower
+  // signal (kernels.h launch_done_signal) instead of an event wait; with
+  // LC_FLAG_NO_TIMING it records no events around the pass either.
+  bool signal = false, timing = true;
+  bool fused = false;  // the version-order and crash-light decisions run as one pass
+  bool light = false;  // the crash-light pass ran (its time is in gap_ms)
+  int64_t n_jit = 0;   // keys still to decide, listed in jit_list (null: every key)
+  const int32_t *jit_list = nullptr;
+  int64_t n_direct = 0;  // keys the fast tier sent straight to d_jit2
+  int32_t n_ovf = 0;     // keys the search tier leaves to the HBM tiers (d_ovf)
+  hipEvent_t before_jit = nullptr;
+  GapPlan early;  // the gap tier launched early (handoff), if it was
+  bool early_launched = false;
+};
+
+// The gap tier's full-decision launch for keys up to max_len records long,
+// nj of them at most (buffers ensured).
+int gap_plan(Run &r, int64_t max_len, int64_t nj, GapPlan &g) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  g.gap_cap = (max_len + 2 + 3) & ~int64_t(3);  // 16-B records
+  g.gap_per_wg = lcdev::gap_tier_ws_bytes(1, g.gap_cap);
+  if (g.gap_per_wg > kGapWsBytes) return 0;  // (the caller checks)
+  g.wg_cap = (int)std::min<int64_t>(
+      (int64_t)kGapMaxWG, std::max<int64_t>(1, (int64_t)(kGapWsBytes / g.gap_per_wg)));
+  // many short keys: one-wave workgroups, four times as many decisions in
+  // flight (10k 200-op keys: 0.78 -> 0.45 ms); few keys are latency-bound
+  // and decide faster with 256 threads each (94 keys: 0.19 vs 0.145 ms)
+  const bool wave_wg = max_len <= kGapWaveMaxLen && nj > kGapWaveMinKeys;
+  g.full_wg = (int)std::min<int64_t>(nj, wave_wg ? 4 * (int64_t)g.wg_cap : g.wg_cap);
+  int rc = ensure(c, d.d_gws, lcdev::gap_tier_ws_bytes(g.full_wg, g.gap_cap));
+  // counterexample intervals: key, lo, hi, gaps, state (int32), nodes
+  // (int64) per invalid key, and one int32 per probe workgroup
+  g.nk = (size_t)nj;
+  if (!rc) rc = ensure(c, d.d_cex, g.nk * (5 * 4 + 8) + 4 * (size_t)g.wg_cap + 64);
+  if (rc) return rc;
+  lcdev::GapJob &job = g.job;
+  job = lcdev::GapJob{};
+  // LC_GAP_PREF_BUDGET (tests): a tiny budget sends every branching decision
+  // through the plain-order rerun
+  const char *pb_env = getenv("LC_GAP_PREF_BUDGET");
+  job.pref_budget = pb_env ? std::max(1, atoi(pb_env)) : lcdev::kGapPrefBudget;
+  const size_t nk = g.nk;
+  job.cex_nodes = reinterpret_cast<int64_t *>(d.d_cex.p);
+  job.cex_key = reinterpret_cast<int32_t *>(d.d_cex.p + 8 * nk);
+  job.cex_lo = reinterpret_cast<uint32_t *>(job.cex_key + nk);
+  job.cex_hi = job.cex_lo + nk;
+  job.cex_gaps = reinterpret_cast<int32_t *>(job.cex_hi + nk);
+  job.cex_state = job.cex_gaps + nk;
+  job.probe = job.cex_state + nk;
+  job.mode = lcdev::kGapFull;
+  job.n_tasks = (int32_t)nj;
+  job.wit = r.want_wit ? r.ao.wit : nullptr;
+  job.wkind = r.want_wit ? r.ao.kind : nullptr;
+  // short keys: one-wave workgroups (barriers nearly free, 4x the decisions
+  // in flight); longer keys: 256 threads share each decision's setup; a
+  // few long keys (C4): 512, whose extra waves halve the setup's record
+  // passes (the matching is one wave either way)
+  g.wide_wg = nj <= kGapWideMaxKeys && max_len >= kGapWideMinLen;
+  job.threads = wave_wg ? 64 : g.wide_wg ? 512 : 256;
+  // Bisect counterexamples in place unless the keys are long and few
+  // enough for multisection rounds to pay (each round costs two launches
+  // and a sync; a probe of a short key costs less than that).
+  job.bisect = max_len < kGapProbeMinLen || 2 * nj > g.wg_cap;
+  // LDS per workgroup: the longest key's skeleton (68 B per record) plus
+  // 8 KB for its matching when that stays within kGapSkelLdsMax (two
+  // workgroups per CU); else room for the matching alone (80 B per record
+  // plus its class table at worst), up to kGapLdsFull, or kGapLdsFew when
+  // there are few keys
+  const int64_t skel = 68 * g.gap_cap + (8 << 10);
+  const int64_t match_cap = nj <= kGapFewKeys ? kGapLdsFew : kGapLdsFull;
+  job.lds_bytes = (int)(skel <= kGapSkelLdsMax ? skel
+                                               : std::min<int64_t>(match_cap, 80 * g.gap_cap + 1040));
+  // LC_GAP_LDS=0 (tests): keep every matching in the HBM workspace
+  g.no_lds = env_is_off("LC_GAP_LDS");
+  if (g.no_lds) job.lds_bytes = 0;
+  return 0;
+}
+
+// Settle what the last call left pending, make room for the per-key lists,
+// and bring the handoff flags and d_status to zero.
+// Invariant: d_status and the flags are zero between calls that completed
+// (status_dirty / flags_dirty false); both are set again here until this
+// call ends cleanly, so after an error return the next call re-zeroes.
+int begin_call(Run &r) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
   (void)settle_status(d);  // before use_fused or h_status is read
   settle_timing(c, d);     // before e0 / ef are recorded again
   d.tot.calls++;
   d.kernel_ms = d.hbm_ms = d.fast_ms = d.jit_ms = d.gap_ms = 0;
   d.n_hbm = d.n_jit = d.n_gap = 0;
   d.malformed = 0;
-  if (n_keys <= 0) return 0;
-  if (n_keys > INT32_MAX) {
+  if (r.n_keys <= 0) return 0;
+  if (r.n_keys > INT32_MAX) {
     set_err(c, "lc_check: more than 2^31-1 keys in one call");
     return -EINVAL;
   }
-  int rc = ensure(c, &d.d_ovf, &d.ovf_cap, sizeof(int32_t) * (size_t)n_keys);
-  if (!rc) rc = ensure(c, &d.d_ovf2, &d.ovf2_cap, sizeof(int32_t) * (size_t)n_keys);
-  if (!rc) rc = ensure(c, &d.d_jit, &d.jit_cap, sizeof(int32_t) * (size_t)n_keys);
-  if (!rc) rc = ensure(c, &d.d_jit2, &d.jit2_cap, sizeof(int32_t) * (size_t)n_keys);
-  if (!rc) rc = ensure(c, &d.d_gap2, &d.gap2_cap, sizeof(int32_t) * (size_t)n_keys);
-  const bool flags_new = d.flags_cap < sizeof(int32_t) * (size_t)n_keys || !d.d_flags;
-  if (!rc) rc = ensure(c, &d.d_flags, &d.flags_cap, sizeof(int32_t) * (size_t)n_keys);
+  const size_t list_bytes = sizeof(int32_t) * (size_t)r.n_keys;
+  int rc = ensure(c, d.d_ovf, list_bytes);
+  if (!rc) rc = ensure(c, d.d_ovf2, list_bytes);
+  if (!rc) rc = ensure(c, d.d_jit, list_bytes);
+  if (!rc) rc = ensure(c, d.d_jit2, list_bytes);
+  if (!rc) rc = ensure(c, d.d_gap2, list_bytes);
+  const bool flags_new = d.d_flags.cap < list_bytes || !d.d_flags.p;
+  if (!rc) rc = ensure(c, d.d_flags, list_bytes);
   if (rc) return rc;
   if (flags_new || d.flags_dirty)  // the flags are all-zero between calls that completed
-    HIP_TRY(c, hipMemsetAsync(d.d_flags, 0, d.flags_cap, st));
+    HIP_TRY(c, hipMemsetAsync(d.d_flags.p, 0, d.d_flags.cap, st));
   d.flags_dirty = false;
-  // With the gap tier on, the fast tier sends keys it can only pass on (no
-  // version on an :ok mutation, a read [nil x], malformed) straight to the
-  // JIT list d_jit2, which the gap tier then appends to.
-  const bool gap_on = !(flags & (LC_FLAG_NO_FAST_PATH | LC_FLAG_NO_GAP_TIER));
-  int64_t n_direct = 0;
   // d_status is zero on entry (the fast tier re-zeroes it; later tiers are
   // followed by a memset).  Until this call ends cleanly, assume it is not.
   if (d.status_dirty)
     HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
   d.status_dirty = true;
-  float ms = 0;
-  // the gap tier's full-decision launch for keys up to max_len records long,
-  // nj of them at most (buffers ensured)
-  auto gap_plan = [&](int64_t max_len, int64_t nj, GapPlan &g) -> int {
-    g.gap_cap = (max_len + 2 + 3) & ~int64_t(3);  // 16-B records
-    g.gap_per_wg = lcdev::gap_tier_ws_bytes(1, g.gap_cap);
-    if (g.gap_per_wg > kGapWsBytes) return 0;  // (the caller checks)
-    g.wg_cap = (int)std::min<int64_t>(
-        (int64_t)kGapMaxWG, std::max<int64_t>(1, (int64_t)(kGapWsBytes / g.gap_per_wg)));
-    // many short keys: one-wave workgroups, four times as many decisions in
-    // flight (10k 200-op keys: 0.78 -> 0.45 ms); few keys are latency-bound
-    // and decide faster with 256 threads each (94 keys: 0.19 vs 0.145 ms)
-    const bool wave_wg = max_len <= kGapWaveMaxLen && nj > kGapWaveMinKeys;
-    g.full_wg = (int)std::min<int64_t>(nj, wave_wg ? 4 * (int64_t)g.wg_cap : g.wg_cap);
-    int rc2 = ensure(c, reinterpret_cast<char **>(&d.d_gws), &d.gws_cap,
-                     lcdev::gap_tier_ws_bytes(g.full_wg, g.gap_cap));
-    // counterexample intervals: key, lo, hi, gaps, state (int32), nodes
-    // (int64) per invalid key, and one int32 per probe workgroup
-    g.nk = (size_t)nj;
-    if (!rc2) rc2 = ensure(c, &d.d_cex, &d.cex_cap, g.nk * (5 * 4 + 8) + 4 * (size_t)g.wg_cap + 64);
-    if (rc2) return rc2;
-    lcdev::GapJob &job = g.job;
-    job = lcdev::GapJob{};
-    // LC_GAP_PREF_BUDGET (tests): a tiny budget sends every branching decision
-    // through the plain-order rerun
-    const char *pb_env = getenv("LC_GAP_PREF_BUDGET");
-    job.pref_budget = pb_env ? std::max(1, atoi(pb_env)) : lcdev::kGapPrefBudget;
-    const size_t nk = g.nk;
-    job.cex_nodes = reinterpret_cast<int64_t *>(d.d_cex);
-    job.cex_key = reinterpret_cast<int32_t *>(d.d_cex + 8 * nk);
-    job.cex_lo = reinterpret_cast<uint32_t *>(job.cex_key + nk);
-    job.cex_hi = job.cex_lo + nk;
-    job.cex_gaps = reinterpret_cast<int32_t *>(job.cex_hi + nk);
-    job.cex_state = job.cex_gaps + nk;
-    job.probe = job.cex_state + nk;
-    job.mode = lcdev::kGapFull;
-    job.n_tasks = (int32_t)nj;
-    const bool wants_wit = wo.wit && wo.kind;
-    job.wit = wants_wit ? wo.wit : nullptr;
-    job.wkind = wants_wit ? wo.kind : nullptr;
-    // short keys: one-wave workgroups (barriers nearly free, 4x the decisions
-    // in flight); longer keys: 256 threads share each decision's setup; a
-    // few long keys (C4): 512, whose extra waves halve the setup's record
-    // passes (the matching is one wave either way)
-    const char *wide_env = getenv("LC_GAP_WIDE");  // A/B: 0 keeps 256
-    g.wide_wg = !(wide_env && wide_env[0] == '0') && nj <= kGapWideMaxKeys &&
-                max_len >= kGapWideMinLen;
-    job.threads = wave_wg ? 64 : g.wide_wg ? 512 : 256;
-    // Bisect counterexamples in place unless the keys are long and few
-    // enough for multisection rounds to pay (each round costs two launches
-    // and a sync; a probe of a short key costs less than that).
-    job.bisect = max_len < kGapProbeMinLen || 2 * nj > g.wg_cap;
-    // LDS per workgroup: the longest key's skeleton (68 B per record) plus
-    // 8 KB for its matching when that stays within kGapSkelLdsMax (two
-    // workgroups per CU); else room for the matching alone (80 B per record
-    // plus its class table at worst), up to kGapLdsFull, or kGapLdsFew when
-    // there are few keys
-    const int64_t skel = 68 * g.gap_cap + (8 << 10);
-    const int64_t match_cap = nj <= kGapFewKeys ? kGapLdsFew : kGapLdsFull;
-    job.lds_bytes = (int)(skel <= kGapSkelLdsMax ? skel
-                                                 : std::min<int64_t>(match_cap, 80 * g.gap_cap + 1040));
-    // LC_GAP_LDS=0 (tests): keep every matching in the HBM workspace
-    const char *lds_env = getenv("LC_GAP_LDS");
-    g.no_lds = lds_env && lds_env[0] == '0';
-    if (g.no_lds) job.lds_bytes = 0;
+  return 0;
+}
+
+// Keys [k0, k0 + nk), records from r0 (relative to d_ops): the witness
+// initialisation (the version order is the witness of every key the fast
+// tier decides) and tier 0, the version-order decision (or the fused
+// pass); the keys it cannot decide are flagged for the later tiers.
+int launch_pass(Run &r, int64_t k0, int64_t nk, int64_t r0, int64_t nrec) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  const lcdev::KParams &p = r.p;
+  const int64_t *off = r.d_off + k0;
+  lc_key_result *out = r.d_out + k0;
+  int32_t *flg = d.d_flags.p + k0;
+  if (r.src.ops32) {  // the native 24-byte pass (no lc_aux outputs)
+    const int64_t *base = r.src.base32 ? r.src.base32 + k0 : nullptr;
+    if (r.fused)
+      HIP_TRY(c, lcdev::launch_fused_tier32(r.src.ops32 + r0, off, base, nk, p, out, flg, d.d_status,
+                                            d.h_handoff_dev, st));
+    else
+      HIP_TRY(c, lcdev::launch_fast_tier32(r.src.ops32 + r0, off, base, nk, p, out, flg, d.d_status,
+                                           d.h_handoff_dev, st));
     return 0;
-  };
-  GapPlan early;              // the gap tier launched early (below), if it was
-  bool early_launched = false;
-  bool light = false;  // the crash-light pass ran (its time is in gap_ms)
-  bool fused = false;  // the version-order and crash-light decisions ran as one pass
-  int64_t n_jit = n_keys;
-  const int32_t *jit_list = nullptr;
-  const bool want_wit = wo.wit && wo.kind;
-  const bool fast_on = !(flags & LC_FLAG_NO_FAST_PATH);
+  }
+  const lc_op *o = r.d_ops + r0;
+  int32_t *wit = r.want_wit ? r.ao.wit + r0 : nullptr;
+  int32_t *kind = r.want_wit ? r.ao.kind + k0 : nullptr;
+  if (r.want_wit)
+    HIP_TRY(c, lcdev::launch_witness_init(o, off, nk, nrec, p, r.fast_on, wit, kind, st));
+  if (!r.fast_on) return 0;
+  if (r.fused)
+    HIP_TRY(c, lcdev::launch_fused_tier(o, off, nk, p, out, flg, d.d_status, d.h_handoff_dev, wit, kind,
+                                        st));
+  else
+    HIP_TRY(c, lcdev::launch_fast_tier(o, off, nk, p, out, flg, d.d_status, d.h_handoff_dev, st));
+  return 0;
+}
+
+// lc_check's pipeline: chunk i's copy is issued, the compute stream waits
+// for it, widens it (24-byte records) and decides its keys while the copy
+// engine moves chunk i + 1.
+int launch_chunks(Run &r, const Chunks &ch) {
+  lc_ctx *c = r.c;
+  hipStream_t st = r.st;
+  for (int i = 0; i < ch.n; i++) {
+    if (int e = ch.issue(i)) return e;
+    HIP_TRY(c, hipStreamWaitEvent(st, ch.ready[i], 0));
+    const int64_t k0 = ch.k[i], nk = ch.k[i + 1] - k0;
+    const int64_t r0 = ch.r[i], nrec = ch.r[i + 1] - r0;
+    if (nk <= 0) continue;
+    const int64_t *base = ch.d_base ? ch.d_base + k0 : nullptr;
+    lc_op *wide = const_cast<lc_op *>(r.d_ops) + r0;
+    if (ch.d_ops32 && !r.src.ops32)
+      HIP_TRY(c, lcdev::launch_widen32(ch.d_ops32 + r0, r.d_off + k0, base, nk, ch.max_len, wide, st));
+    if (ch.d_ops16)
+      HIP_TRY(c, lcdev::launch_widen16(ch.d_ops16 + r0, r.d_off + k0, base, nk, ch.max_len, wide, st));
+    if (int e = launch_pass(r, k0, nk, r0, nrec)) return e;
+  }
+  return 0;
+}
+
+// The first pass over every key, served by the resident grid, by one launch
+// or by lc_check's chunk pipeline, and waited for; d.fast_ms is its time
+// (or timing_pending).  *handed: some key goes on to the later tiers.
+//
+// Hot paths (same HIP calls, same order, same streams as ever; add none):
+//  * lc_check_device, signal path, every key decided: [event e0] pass
+//    [event ef] done-signal, all on st, then spinning on h_done;
+//  * the resident request: a query of st, then host-mapped words only;
+//  * native lc_check_device32: as the first with the 24-byte pass.
+// A live resident grid is stopped before any other work of the library runs
+// on its device: here when this call does not use it, and in the grid's arm
+// before the later tiers' first launch.
+int first_pass(Run &r, bool *handed) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  *handed = false;
   d.maybe_invalid = true;
-  if (fast_on) {
+  if (r.fast_on) {
     // Crash-heavy batches (most keys carry crashed writes/CAS: every key goes
     // on to the crash-light decision) take the fused pass, which reads each
     // key's records once for both decisions; others the version-order tier,
     // whose smaller register budget keeps 7 workgroups per CU.  Chosen from
     // the previous call on this device (LC_FUSED=0/1 forces it).
     const char *fenv = getenv("LC_FUSED");
-    fused = gap_on && (fenv ? fenv[0] == '1' : d.use_fused);
+    r.fused = r.gap_on && (fenv ? fenv[0] == '1' : d.use_fused);
     // Only when some workgroup raised h_handoff is the count copied back.
     __atomic_store_n(d.h_handoff, 0, __ATOMIC_RELEASE);
     d.flags_dirty = true;  // until the handoff (if any) is compacted
   }
-  // keys [k0, k0 + nk), records from r0 (relative to d_ops): the witness
-  // initialisation (the version order is the witness of every key the fast
-  // tier decides) and tier 0, the version-order decision (or the fused
-  // pass); the keys it cannot decide are flagged for the later tiers
-  // A call with one pass launch (no chunks) returns on the pass's follower
-  // signal (kernels.h launch_done_signal) instead of an event wait; with
-  // LC_FLAG_NO_TIMING it records no events around the pass either.
-  const bool signal = !wo.chunks && fast_on && n_keys > 0;
-  bool timing = !signal || !(flags & LC_FLAG_NO_TIMING);
   // the resident grid serves lc_check_device's plain version-order pass on
   // a batch of at most one key per resident workgroup (res_request); any
   // other call on this device first stops a live grid
   if (d.res_cap < 0) d.res_cap = lcdev::fast_resident_capacity();
-  const bool resident = signal && !fused && !want_wit && !wo.ops32 && !d.res_broken &&
-                        n_keys <= d.res_cap && !resident_off();
-  int res_rc = 1;  // 0: the grid decided the pass
-  double res_ms = 0;
+  const bool resident = r.signal && !r.fused && !r.want_wit && !r.src.ops32 && !d.res_broken &&
+                        r.n_keys <= d.res_cap && !env_is_off("LC_RESIDENT");
+  bool served = false;  // the grid decided the pass
   if (resident) {
-    res_rc = res_request(c, d, d_ops, d_off, n_keys, p, d_out, st, &res_ms);
-    if (res_rc < 0) return res_rc;
-    if (res_rc == 1) {
-      // not served (the grid may have decided part of it): launch instead,
-      // from the state the pass starts from
-      HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
-      HIP_TRY(c, hipMemsetAsync(d.d_flags, 0, d.flags_cap, st));
-      __atomic_store_n(d.h_handoff, 0, __ATOMIC_RELEASE);
+    double res_ms = 0;
+    const int rc = res_request(c, d, r.d_ops, r.d_off, r.n_keys, r.p, r.d_out, st, &res_ms);
+    if (rc < 0) return rc;
+    served = rc == 0;
+    if (served) {
+      r.timing = true;  // (the grid's device clock: free)
+      d.fast_ms = res_ms;
     } else {
-      timing = true;  // (the grid's device clock: free)
+      // not served (the grid may have decided part of it): launch instead,
+      // from the state the pass starts from — zeroed status and flags
+      HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
+      HIP_TRY(c, hipMemsetAsync(d.d_flags.p, 0, d.d_flags.cap, st));
+      __atomic_store_n(d.h_handoff, 0, __ATOMIC_RELEASE);
     }
   } else if (d.res_grid) {
     if (int e = res_stop(c, d)) return e;
   }
-  auto first_pass = [&](int64_t k0, int64_t nk, int64_t r0, int64_t nrec) -> int {
-    const int64_t *off = d_off + k0;
-    if (wo.ops32) {  // the native 24-byte pass (no lc_aux outputs)
-      const int64_t *base = wo.base32 ? wo.base32 + k0 : nullptr;
-      if (fused)
-        HIP_TRY(c, lcdev::launch_fused_tier32(wo.ops32 + r0, off, base, nk, p, d_out + k0,
-                                              d.d_flags + k0, d.d_status, d.h_handoff_dev, st));
-      else
-        HIP_TRY(c, lcdev::launch_fast_tier32(wo.ops32 + r0, off, base, nk, p, d_out + k0,
-                                             d.d_flags + k0, d.d_status, d.h_handoff_dev, st));
-      return 0;
-    }
-    const lc_op *o = d_ops + r0;
-    int32_t *wit = want_wit ? wo.wit + r0 : nullptr;
-    int32_t *kind = want_wit ? wo.kind + k0 : nullptr;
-    if (want_wit)
-      HIP_TRY(c, lcdev::launch_witness_init(o, off, nk, nrec, p, fast_on, wit, kind, st));
-    if (!fast_on) return 0;
-    if (fused)
-      HIP_TRY(c, lcdev::launch_fused_tier(o, off, nk, p, d_out + k0, d.d_flags + k0, d.d_status,
-                                          d.h_handoff_dev, wit, kind, st));
-    else
-      HIP_TRY(c, lcdev::launch_fast_tier(o, off, nk, p, d_out + k0, d.d_flags + k0, d.d_status,
-                                         d.h_handoff_dev, st));
-    return 0;
-  };
-  if (res_rc == 0) {
-    // (decided by the resident grid)
-  } else if (timing) {
-    HIP_TRY(c, hipEventRecord(d.e0, st));
-  }
-  if (res_rc == 0) {
-  } else if (const Chunks *ch = wo.chunks) {
-    // lc_check's pipeline: chunk i's copy is issued, the compute stream
-    // waits for it, widens it (24-byte records) and decides its keys while
-    // the copy engine moves chunk i + 1
-    for (int i = 0; i < ch->n; i++) {
-      if (int e = ch->issue(i)) return e;
-      HIP_TRY(c, hipStreamWaitEvent(st, ch->ready[i], 0));
-      const int64_t k0 = ch->k[i], nk = ch->k[i + 1] - k0;
-      const int64_t r0 = ch->r[i], nrec = ch->r[i + 1] - r0;
-      if (nk <= 0) continue;
-      if (ch->d_ops32 && !wo.ops32)
-        HIP_TRY(c, lcdev::launch_widen32(ch->d_ops32 + r0, d_off + k0,
-                                         ch->d_base ? ch->d_base + k0 : nullptr, nk, ch->max_len,
-                                         const_cast<lc_op *>(d_ops) + r0, st));
-      if (ch->d_ops16)
-        HIP_TRY(c, lcdev::launch_widen16(ch->d_ops16 + r0, d_off + k0,
-                                         ch->d_base ? ch->d_base + k0 : nullptr, nk, ch->max_len,
-                                         const_cast<lc_op *>(d_ops) + r0, st));
-      if (int e = first_pass(k0, nk, r0, nrec)) return e;
-    }
-  } else if (int e = first_pass(0, n_keys, 0, wo.n_records)) {
-    return e;
-  }
-  if (fast_on) {
-    if (res_rc == 0) {
-      // (completed already)
-    } else if (timing) {
+  if (served) {
+    *handed = __atomic_load_n(d.h_handoff, __ATOMIC_ACQUIRE) != 0;
+    if (*handed) {
+      // the grid's exit publishes the flags and the status words to the
+      // later tiers (and frees its CUs); their times are measured from here
+      if (int e = res_stop(c, d)) return e;
+      HIP_TRY(c, hipEventRecord(d.e0, st));
       HIP_TRY(c, hipEventRecord(d.ef, st));
     }
-    if (res_rc == 0) {
-    } else if (signal) {
+  } else {
+    if (r.timing) HIP_TRY(c, hipEventRecord(d.e0, st));
+    if (r.src.chunks) {
+      if (int e = launch_chunks(r, *r.src.chunks)) return e;
+    } else if (int e = launch_pass(r, 0, r.n_keys, 0, r.ao.n_records)) {
+      return e;
+    }
+    if (!r.fast_on) {  // (witness initialisation only: every key goes to the search tiers)
+      HIP_TRY(c, hipEventRecord(d.ef, st));
+      return 0;
+    }
+    if (r.timing) HIP_TRY(c, hipEventRecord(d.ef, st));
+    if (r.signal) {
       HIP_TRY(c, lcdev::launch_done_signal(d.h_done_dev, ++d.seq, st));
       if (int e = wait_done(c, d, d.seq, st)) return e;
     } else {
       HIP_TRY(c, hipEventSynchronize(d.ef));
     }
-    n_jit = 0;
-    jit_list = d.d_jit;
-    const bool handed = __atomic_load_n(d.h_handoff, __ATOMIC_ACQUIRE) != 0;
-    if (res_rc == 0) {
-      d.fast_ms = res_ms;
-      if (handed) {
-        // the grid's exit publishes the flags and the status words to the
-        // later tiers (and frees its CUs); their times are measured from here
-        if (int e = res_stop(c, d)) return e;
-        HIP_TRY(c, hipEventRecord(d.e0, st));
-        HIP_TRY(c, hipEventRecord(d.ef, st));
-      }
-    } else if (signal && !handed) {
+    *handed = __atomic_load_n(d.h_handoff, __ATOMIC_ACQUIRE) != 0;
+    if (r.signal && !*handed) {
       // every key decided: the pass's event time (if any) is read later
-      d.timing_pending = timing;
+      d.timing_pending = r.timing;
     } else {
-      if (!timing) {
+      if (!r.timing) {
         // the later tiers' times are measured from here (the pass untimed)
         HIP_TRY(c, hipEventRecord(d.e0, st));
         HIP_TRY(c, hipEventRecord(d.ef, st));
       }
+      float ms = 0;
       HIP_TRY(c, hipEventSynchronize(d.ef));
       HIP_TRY(c, hipEventElapsedTime(&ms, d.e0, d.ef));
       d.fast_ms = ms;
     }
-    if (!handed) {
-      d.flags_dirty = false;  // no key raised its flag
-      // the version-order tier and the fused pass decide valid keys only
-      // (they hand invalid ones on for their counterexamples)
-      d.maybe_invalid = false;
-    }
-    if (fused && !handed) {
-      // every key decided in the one pass: were most of them crash-light?
-      // (the answer picks the next call's pass; copied now, read later)
-      // (one launch: the count to mapped host memory, d_status zeroed behind
-      // it now — while the host returns — not at the start of the next call)
-      HIP_TRY(c, lcdev::launch_status_settle(d.d_status, d.h_handoff_dev + 1, st));
-      HIP_TRY(c, hipEventRecord(d.es, st));
-      d.st_pending = true;
-      d.st_keys = n_keys;
-      d.status_dirty = false;
-    }
-    if (handed) {
-      // the native 24-byte pass: the later tiers read 48-byte records
-      if (wo.widen)
-        if (int e = wo.widen(&d_ops)) return e;
-      HIP_TRY(c, lcdev::launch_handoff_compact(d.d_flags, d_off, n_keys, gap_on ? 1 : 0, d.d_jit,
-                                               d.d_jit2, d.d_status, want_wit ? wo.kind : nullptr,
-                                               st));
-      d.flags_dirty = false;  // the compaction clears every flag it reads
-      // the crash-light pass reads the list and its length from the device:
-      // no host round trip between the compaction and it.  After the fused
-      // pass too: the keys it hands over are invalid or beyond the in-place
-      // decision, and the light pass names an invalid version-pinned key's
-      // first failure (check_kernel.hip, first_failure), so every path gives
-      // the same results
-      if (gap_on) {
-        HIP_TRY(c, lcdev::launch_gap_light(d_ops, d_off, d.d_jit, n_keys, p, d_out, d.d_gap2,
-                                           d.d_status, want_wit ? wo.wit : nullptr,
-                                           want_wit ? wo.kind : nullptr, st));
-        HIP_TRY(c, hipEventRecord(d.el, st));
-        // Launched early: a few keys, one longer than the light pass holds
-        // (kFastMaxRecords: it goes on to the gap tier proper) and the
-        // shard's offsets in host memory — the full decisions start right
-        // behind the light pass, sized from those offsets, their count read
-        // on the device (GapJob::n_tasks_dev), instead of after a host round
-        // trip for the status.  Same decisions, same results.
-        if (wo.h_off && n_keys <= kGapWideMaxKeys) {
-          int64_t ml = 0;
-          for (int64_t k = 0; k < n_keys; k++) ml = std::max<int64_t>(ml, wo.h_off[k + 1] - wo.h_off[k]);
-          const char *ee = getenv("LC_GAP_EARLY");  // A/B: 0 waits for the status
-          if (ml > lcdev::kFastMaxRecords && !(ee && ee[0] == '0')) {
-            if (int e = gap_plan(ml, n_keys, early)) return e;
-            if (early.gap_per_wg <= kGapWsBytes) {
-              early.job.n_tasks_dev = &d.d_status->n_gap2;
-              HIP_TRY(c, lcdev::launch_gap_tier(d_ops, d_off, d.d_gap2, p, d_out, d.d_gws,
-                                                early.full_wg, early.gap_cap, d.d_jit2, d.d_status,
-                                                early.job, st));
-              HIP_TRY(c, hipEventRecord(d.eg, st));
-              early_launched = true;
-            }
-          }
+  }
+  r.n_jit = 0;
+  r.jit_list = d.d_jit.p;
+  if (*handed) return 0;
+  d.flags_dirty = false;  // no key raised its flag
+  // the version-order tier and the fused pass decide valid keys only
+  // (they hand invalid ones on for their counterexamples)
+  d.maybe_invalid = false;
+  if (r.fused) {
+    // every key decided in the one pass: were most of them crash-light?
+    // (the answer picks the next call's pass; copied now, read later)
+    // (one launch: the count to mapped host memory, d_status zeroed behind
+    // it now — while the host returns — not at the start of the next call)
+    HIP_TRY(c, lcdev::launch_status_settle(d.d_status, d.h_handoff_dev + 1, st));
+    HIP_TRY(c, hipEventRecord(d.es, st));
+    d.st_pending = true;
+    d.st_keys = r.n_keys;
+    d.status_dirty = false;
+  }
+  return 0;
+}
+
+// Some key was handed over: the 48-byte records (a native 24-byte pass), the
+// compaction of the flags into lists, the crash-light pass over the gap
+// tier's list, the gap tier itself when it can be sized already, and the
+// status read that tells what is left (n_jit / jit_list / n_direct).
+// (h_status is free until that read: lc_check_device32's widen uses it as
+// scratch for the record count.)
+int handoff(Run &r) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  const int64_t n_keys = r.n_keys;
+  int32_t *wit = r.want_wit ? r.ao.wit : nullptr, *kind = r.want_wit ? r.ao.kind : nullptr;
+  // the native 24-byte pass: the later tiers read 48-byte records
+  if (r.src.widen)
+    if (int e = r.src.widen(&r.d_ops)) return e;
+  HIP_TRY(c, lcdev::launch_handoff_compact(d.d_flags.p, r.d_off, n_keys, r.gap_on ? 1 : 0, d.d_jit.p,
+                                           d.d_jit2.p, d.d_status, kind, st));
+  d.flags_dirty = false;  // the compaction clears every flag it reads
+  // the crash-light pass reads the list and its length from the device:
+  // no host round trip between the compaction and it.  After the fused
+  // pass too: the keys it hands over are invalid or beyond the in-place
+  // decision, and the light pass names an invalid version-pinned key's
+  // first failure (check_kernel.hip, first_failure), so every path gives
+  // the same results
+  if (r.gap_on) {
+    HIP_TRY(c, lcdev::launch_gap_light(r.d_ops, r.d_off, d.d_jit.p, n_keys, r.p, r.d_out, d.d_gap2.p,
+                                       d.d_status, wit, kind, st));
+    HIP_TRY(c, hipEventRecord(d.el, st));
+    // Launched early: a few keys, one longer than the light pass holds
+    // (kFastMaxRecords: it goes on to the gap tier proper) and the
+    // shard's offsets in host memory — the full decisions start right
+    // behind the light pass, sized from those offsets, their count read
+    // on the device (GapJob::n_tasks_dev), instead of after a host round
+    // trip for the status.  Same decisions, same results.
+    if (r.src.h_off && n_keys <= kGapWideMaxKeys) {
+      int64_t ml = 0;
+      for (int64_t k = 0; k < n_keys; k++)
+        ml = std::max<int64_t>(ml, r.src.h_off[k + 1] - r.src.h_off[k]);
+      // LC_GAP_EARLY=0 (A/B): wait for the status
+      if (ml > lcdev::kFastMaxRecords && !env_is_off("LC_GAP_EARLY")) {
+        GapPlan &early = r.early;
+        if (int e = gap_plan(r, ml, n_keys, early)) return e;
+        if (early.gap_per_wg <= kGapWsBytes) {
+          early.job.n_tasks_dev = &d.d_status->n_gap2;
+          HIP_TRY(c, lcdev::launch_gap_tier(r.d_ops, r.d_off, d.d_gap2.p, r.p, r.d_out, d.d_gws.p,
+                                            early.full_wg, early.gap_cap, d.d_jit2.p, d.d_status,
+                                            early.job, st));
+          HIP_TRY(c, hipEventRecord(d.eg, st));
+          r.early_launched = true;
         }
       }
-      HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus),
-                                hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      n_direct = d.h_status->n_jit2;
-      if (fused) lcdev::light_count(*d.h_status);
-      if (gap_on) {
-        // fused: were most keys crash-light?  Else: most keys handed to the
-        // gap tier: the next call fuses the passes
-        d.use_fused = fused ? 4 * (int64_t)d.h_status->n_light > n_keys
-                            : 2 * (int64_t)d.h_status->n_jit > n_keys;
-        light = true;
-        HIP_TRY(c, hipEventElapsedTime(&ms, d.ef, d.el));
-        d.gap_ms = ms;
-        d.n_gap = fused ? d.h_status->n_light : d.h_status->n_jit;
-        n_jit = d.h_status->n_gap2;  // what the gap tier proper still has to decide
-        jit_list = d.d_gap2;
-      } else {
-        n_jit = d.h_status->n_jit;
-      }
     }
-  } else {
-    HIP_TRY(c, hipEventRecord(d.ef, st));
   }
-  if (n_jit == 0 && n_direct == 0) {
-    d.kernel_ms = d.fast_ms + d.gap_ms;
-    if (!d.timing_pending && timing) {
-      d.tot.timed_calls++;
-      d.tot.fast_kernel_ms += d.fast_ms;
-      d.tot.kernel_ms += d.kernel_ms;
-    }
-    // after a handoff d_status is not zero: cleared behind this call's work
-    // (the host has read it), not in front of the next call's
-    if (light) HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
-    d.status_dirty = false;
+  if (int e = read_status(c, d, st)) return e;
+  r.n_direct = d.h_status->n_jit2;
+  if (r.fused) lcdev::light_count(*d.h_status);
+  if (!r.gap_on) {
+    r.n_jit = d.h_status->n_jit;
     return 0;
   }
-  hipEvent_t before_jit = light ? d.el : d.ef;
-  const int64_t gap_cap = ((int64_t)d.h_status->max_len + 2 + 3) & ~int64_t(3);  // 16-B records
-  const size_t gap_per_wg = lcdev::gap_tier_ws_bytes(1, gap_cap);
-  if (gap_on && (n_jit == 0 || gap_per_wg > kGapWsBytes)) {
-    // no gap-tier pass: its queue (if any) joins the direct keys for the JIT
-    if (n_jit > 0)
-      HIP_TRY(c, hipMemcpyAsync(d.d_jit2 + n_direct, jit_list, sizeof(int32_t) * (size_t)n_jit,
-                                hipMemcpyDeviceToDevice, st));
-    n_jit += n_direct;
-    jit_list = d.d_jit2;
-  } else if (gap_on) {
-    // tier 1: gap matching for version-pinned keys (crashed writes/CAS, long
-    // keys, invalid keys); what it cannot decide goes on to the JIT search
-    GapPlan g;
-    if (early_launched) {
-      g = early;  // launched behind the light pass; the status read since includes it
-    } else {
-      if (int e = gap_plan(d.h_status->max_len, n_jit, g)) return e;
-      HIP_TRY(c, lcdev::launch_gap_tier(d_ops, d_off, jit_list, p, d_out, d.d_gws, g.full_wg,
-                                        g.gap_cap, d.d_jit2, d.d_status, g.job, st));
-      HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus),
-                                hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
+  // fused: were most keys crash-light?  Else: most keys handed to the
+  // gap tier: the next call fuses the passes
+  d.use_fused = r.fused ? 4 * (int64_t)d.h_status->n_light > n_keys
+                        : 2 * (int64_t)d.h_status->n_jit > n_keys;
+  r.light = true;
+  float ms = 0;
+  HIP_TRY(c, hipEventElapsedTime(&ms, d.ef, d.el));
+  d.gap_ms = ms;
+  d.n_gap = r.fused ? d.h_status->n_light : d.h_status->n_jit;
+  r.n_jit = d.h_status->n_gap2;  // what the gap tier proper still has to decide
+  r.jit_list = d.d_gap2.p;
+  return 0;
+}
+
+// Counterexamples of long keys (n_cex open intervals after the full
+// decisions): P probes per interval per round, over the whole GPU, then the
+// witness pass.
+int gap_counterexamples(Run &r, GapPlan &g, int32_t n_cex, int64_t gap_cap) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  lcdev::GapJob &job = g.job;
+  job.mode = lcdev::kGapProbe;
+  // the probes of a few long keys: 512-thread workgroups as for their full
+  // decisions (half as many probes per round; C4's interval still closes in
+  // two rounds)
+  job.threads = g.wide_wg ? 512 : 256;
+  job.lds_bytes = g.no_lds ? 0 : kGapLdsProbe;
+  // as many probes as run at once: a round's time is its slowest batch
+  // of resident workgroups, and a second batch doubles it for a few
+  // more cuts (C4 invalid: 1,024 probes = two batches of 512 resident)
+  const int resident = lcdev::gap_tier_resident(job.lds_bytes, job.threads);
+  job.P = (resident / n_cex >= 2 ? std::min(resident, g.wg_cap) : g.wg_cap) / n_cex;
+  job.n_tasks = n_cex * job.P;
+  if (int rc = ensure(c, d.d_gws, lcdev::gap_tier_ws_bytes(job.n_tasks, gap_cap))) return rc;
+  for (int round = 0;; round++) {
+    if (round == kGapMaxRounds) {
+      // cannot happen (each round cuts an interval by P + 1 >= 3); the
+      // JIT tier decides whatever is still open rather than the call fail
+      job.give_up = 1;
+      HIP_TRY(c, lcdev::launch_gap_narrow(r.d_ops, r.d_off, n_cex, r.d_out, d.d_jit2.p, d.d_status, job,
+                                          st));
+      break;
     }
-    lcdev::GapJob &job = g.job;
-    job.n_tasks_dev = nullptr;
-    const int wg_cap = g.wg_cap;
-    const bool wide_wg = g.wide_wg, no_lds = g.no_lds;
-    const int32_t n_cex = d.h_status->n_cex;
-    if (n_cex > 0) {
-      // counterexamples of long keys: P probes per interval per round, over
-      // the whole GPU
-      job.mode = lcdev::kGapProbe;
-      // the probes of a few long keys: 512-thread workgroups as for their full
-      // decisions (half as many probes per round; C4's interval still closes in
-      // two rounds)
-      const char *wp_env = getenv("LC_GAP_WIDE_PROBE");  // A/B: 0 keeps 256
-      job.threads = wide_wg && !(wp_env && wp_env[0] == '0') ? 512 : 256;
-      job.lds_bytes = no_lds ? 0 : kGapLdsProbe;
-      // as many probes as run at once: a round's time is its slowest batch
-      // of resident workgroups, and a second batch doubles it for a few
-      // more cuts (C4 invalid: 1,024 probes = two batches of 512 resident)
-      const int resident = lcdev::gap_tier_resident(job.lds_bytes, job.threads);
-      job.P = (resident / n_cex >= 2 ? std::min(resident, wg_cap) : wg_cap) / n_cex;
-      job.n_tasks = n_cex * job.P;
-      rc = ensure(c, reinterpret_cast<char **>(&d.d_gws), &d.gws_cap,
-                  lcdev::gap_tier_ws_bytes(job.n_tasks, gap_cap));
-      if (rc) return rc;
-      for (int round = 0;; round++) {
-        if (round == kGapMaxRounds) {
-          // cannot happen (each round cuts an interval by P + 1 >= 3); the
-          // JIT tier decides whatever is still open rather than the call fail
-          job.give_up = 1;
-          HIP_TRY(c, lcdev::launch_gap_narrow(d_ops, d_off, n_cex, d_out, d.d_jit2, d.d_status,
-                                              job, st));
-          break;
-        }
-        HIP_TRY(c, hipMemsetAsync(&d.d_status->n_open, 0, sizeof(int32_t), st));
-        HIP_TRY(c, lcdev::launch_gap_tier(d_ops, d_off, nullptr, p, d_out, d.d_gws, job.n_tasks,
-                                          gap_cap, d.d_jit2, d.d_status, job, st));
-        HIP_TRY(c, lcdev::launch_gap_narrow(d_ops, d_off, n_cex, d_out, d.d_jit2, d.d_status,
-                                            job, st));
-        HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus),
-                                  hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (d.h_status->n_open == 0) break;
-      }
-      if (want_wit) {
-        // the witness of each closed counterexample's last linearizable prefix
-        job.mode = lcdev::kGapWitness;
-        job.P = 1;
-        job.n_tasks = n_cex;
-        HIP_TRY(c, lcdev::launch_gap_tier(d_ops, d_off, nullptr, p, d_out, d.d_gws,
-                                          std::min<int>(n_cex, wg_cap), gap_cap, d.d_jit2,
-                                          d.d_status, job, st));
-      }
-    }
-    if (!early_launched || n_cex > 0) {  // (launched early and done: the status is current)
-      HIP_TRY(c, hipEventRecord(d.eg, st));
-      HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus),
-                                hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-    }
-    HIP_TRY(c, hipEventElapsedTime(&ms, d.ef, d.eg));
-    d.gap_ms = ms;
-    if (!light && !fused) d.n_gap = n_jit;
-    n_jit = d.h_status->n_jit2;
-    jit_list = d.d_jit2;
-    before_jit = d.eg;
+    HIP_TRY(c, hipMemsetAsync(&d.d_status->n_open, 0, sizeof(int32_t), st));
+    HIP_TRY(c, lcdev::launch_gap_tier(r.d_ops, r.d_off, nullptr, r.p, r.d_out, d.d_gws.p, job.n_tasks,
+                                      gap_cap, d.d_jit2.p, d.d_status, job, st));
+    HIP_TRY(c, lcdev::launch_gap_narrow(r.d_ops, r.d_off, n_cex, r.d_out, d.d_jit2.p, d.d_status, job,
+                                        st));
+    if (int e = read_status(c, d, st)) return e;
+    if (d.h_status->n_open == 0) break;
   }
+  if (r.want_wit) {
+    // the witness of each closed counterexample's last linearizable prefix
+    job.mode = lcdev::kGapWitness;
+    job.P = 1;
+    job.n_tasks = n_cex;
+    HIP_TRY(c, lcdev::launch_gap_tier(r.d_ops, r.d_off, nullptr, r.p, r.d_out, d.d_gws.p,
+                                      std::min<int>(n_cex, g.wg_cap), gap_cap, d.d_jit2.p, d.d_status,
+                                      job, st));
+  }
+  return 0;
+}
+
+// Tier 1: gap matching for version-pinned keys (crashed writes/CAS, long
+// keys, invalid keys); what it cannot decide goes on to the JIT search, whose
+// list (n_jit / jit_list) and start event (before_jit) this leaves.
+int gap_tier(Run &r) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  r.before_jit = r.light ? d.el : d.ef;
+  if (!r.gap_on) return 0;
+  const int64_t gap_cap = ((int64_t)d.h_status->max_len + 2 + 3) & ~int64_t(3);  // 16-B records
+  if (r.n_jit == 0 || lcdev::gap_tier_ws_bytes(1, gap_cap) > kGapWsBytes) {
+    // no gap-tier pass: its queue (if any) joins the direct keys for the JIT
+    if (r.n_jit > 0)
+      HIP_TRY(c, hipMemcpyAsync(d.d_jit2.p + r.n_direct, r.jit_list, sizeof(int32_t) * (size_t)r.n_jit,
+                                hipMemcpyDeviceToDevice, st));
+    r.n_jit += r.n_direct;
+    r.jit_list = d.d_jit2.p;
+    return 0;
+  }
+  GapPlan g;
+  if (r.early_launched) {
+    g = r.early;  // launched behind the light pass; the status read since includes it
+  } else {
+    if (int e = gap_plan(r, d.h_status->max_len, r.n_jit, g)) return e;
+    HIP_TRY(c, lcdev::launch_gap_tier(r.d_ops, r.d_off, r.jit_list, r.p, r.d_out, d.d_gws.p, g.full_wg,
+                                      g.gap_cap, d.d_jit2.p, d.d_status, g.job, st));
+    if (int e = read_status(c, d, st)) return e;
+  }
+  g.job.n_tasks_dev = nullptr;
+  const int32_t n_cex = d.h_status->n_cex;
+  if (n_cex > 0)
+    if (int e = gap_counterexamples(r, g, n_cex, gap_cap)) return e;
+  if (!r.early_launched || n_cex > 0) {  // (launched early and done: the status is current)
+    HIP_TRY(c, hipEventRecord(d.eg, st));
+    if (int e = read_status(c, d, st)) return e;
+  }
+  float ms = 0;
+  HIP_TRY(c, hipEventElapsedTime(&ms, d.ef, d.eg));
+  d.gap_ms = ms;
+  if (!r.light && !r.fused) d.n_gap = r.n_jit;
+  r.n_jit = d.h_status->n_jit2;
+  r.jit_list = d.d_jit2.p;
+  r.before_jit = d.eg;
+  return 0;
+}
+
+// Tier 2, the frontier search of the keys still listed: straight to the
+// cooperative HBM tier (n_ovf of them in d_ovf) or through the LDS tier,
+// which leaves the keys that outgrow it there.
+int search_tier(Run &r) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  const int64_t n_jit = r.n_jit;
+  float ms = 0;
   d.n_jit = n_jit;
   // Few keys for the frontier search (at most kJitDirectMaxKeys: one 4-wave
   // workgroup per key, all resident at once) go straight to the cooperative
@@ -1012,90 +1068,132 @@ int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off,
   // 1,000 x 200 2.4 -> 1.8 ms, 64 x 1,000 10.1 -> 6.5 ms; but 4,000 x 100
   // 1.0 -> 3.0 ms, where the LDS tier's four keys per workgroup win.
   // LC_JIT_DIRECT=0 (A/B) keeps the LDS tier first.
-  const char *direct_env = getenv("LC_JIT_DIRECT");
   // (not with LC_FLAG_NO_FAST_PATH, whose JIT list is implicit: every key)
-  const bool direct = !(direct_env && direct_env[0] == '0') && n_jit > 0 && jit_list &&
-                      n_jit <= kJitDirectMaxKeys && !(flags & LC_FLAG_NO_HBM_RETRY);
-  if (direct) {
-    HIP_TRY(c, hipMemcpyAsync(d.d_ovf, jit_list, sizeof(int32_t) * (size_t)n_jit,
+  const bool direct = !env_is_off("LC_JIT_DIRECT") && n_jit > 0 && r.jit_list &&
+                      n_jit <= kJitDirectMaxKeys && !(r.flags & LC_FLAG_NO_HBM_RETRY);
+  if (direct)
+    HIP_TRY(c, hipMemcpyAsync(d.d_ovf.p, r.jit_list, sizeof(int32_t) * (size_t)n_jit,
                               hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipEventElapsedTime(&ms, d.e0, before_jit));
-    d.kernel_ms = ms;
-  } else if (n_jit == 0) {
-    HIP_TRY(c, hipEventElapsedTime(&ms, d.e0, before_jit));
+  if (direct || n_jit == 0) {
+    HIP_TRY(c, hipEventElapsedTime(&ms, d.e0, r.before_jit));
     d.kernel_ms = ms;
   } else {
-    // tier 2: JIT search with the frontier in SGPRs / LDS
-    HIP_TRY(c, lcdev::launch_lds_tier(d_ops, d_off, jit_list, n_jit, p, d_out,
-                                      d.d_ovf, d.d_status, st));
+    // JIT search with the frontier in SGPRs / LDS
+    HIP_TRY(c, lcdev::launch_lds_tier(r.d_ops, r.d_off, r.jit_list, n_jit, r.p, r.d_out, d.d_ovf.p,
+                                      d.d_status, st));
     HIP_TRY(c, hipEventRecord(d.e1, st));
-    HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus),
-                              hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipEventElapsedTime(&ms, before_jit, d.e1));
+    if (int e = read_status(c, d, st)) return e;
+    HIP_TRY(c, hipEventElapsedTime(&ms, r.before_jit, d.e1));
     d.jit_ms = ms;
     HIP_TRY(c, hipEventElapsedTime(&ms, d.e0, d.e1));
     d.kernel_ms = ms;
   }
   d.malformed = d.h_status->malformed;
-  const int32_t n_ovf = direct ? (int32_t)n_jit : d.h_status->n_overflow;
-  d.n_hbm = n_ovf;
-  if (n_ovf > 0 && !(flags & LC_FLAG_NO_HBM_RETRY)) {
-    int32_t n_list = n_ovf;
-    int32_t *list = d.d_ovf, *next = d.d_ovf2;
-    HIP_TRY(c, hipEventRecord(d.e1, st));
-    // LC_HBM_COOP (test/A-B knob): 0 one wavefront per key throughout,
-    // 4 / 16 a workgroup of that many wavefronts per key throughout; default:
-    // 8 for at most 512 keys (two workgroups per CU), else 4.  (Round 1 used
-    // one wavefront per key beyond 4,096 keys; with the LDS tables the
-    // 4-wave workgroups win there too: version-less 10,000 x 1,000 at
-    // concurrency 20, HBM tier 128 -> 98 ms, tools/hbm_width_large.py.)
-    const char *coop_env = getenv("LC_HBM_COOP");
-    const int coop_mode = coop_env ? atoi(coop_env) : 1;
-    for (int tier = 0; tier < kHbmTiers && n_list > 0; tier++) {
-      int wpk = coop_mode == 1 ? (n_list <= kHbmCoop8MaxKeys ? 8 : 4) : coop_mode;
-      const bool coop = wpk == 4 || wpk == 8 || wpk == 16;
-      // workgroups: at most the resident ones (keys are claimed dynamically)
-      const int resident = wpk == 16 ? kHbmCoop16Resident : wpk == 8 ? 512
-                           : wpk == 4 ? kHbmCoop4Resident : kHbmWaves[tier];
-      const int waves = std::min<int>(std::min(kHbmWaves[tier], resident), n_list);
-      const size_t ws = lcdev::hbm_tier_ws_bytes(waves, kHbmCap[tier]);
-      rc = ensure(c, reinterpret_cast<char **>(&d.d_ws), &d.ws_cap, ws);
-      if (rc) return rc;
-      HIP_TRY(c, hipMemsetAsync(&d.d_status->n_overflow2, 0, sizeof(int32_t), st));
-      HIP_TRY(c, hipMemsetAsync(&d.d_status->hbm_next, 0, sizeof(int32_t), st));
-      const int last = tier == kHbmTiers - 1;
-      if (coop)
-        HIP_TRY(c, lcdev::launch_hbm_coop(d_ops, d_off, list, n_list, p, d_out, d.d_ws, waves,
-                                          kHbmCap[tier], next, &d.d_status->n_overflow2,
-                                          &d.d_status->malformed, &d.d_status->hbm_next, last,
-                                          wpk, st));
-      else
-        HIP_TRY(c, lcdev::launch_hbm_tier(d_ops, d_off, list, n_list, p,
-                                          d_out, d.d_ws, waves, kHbmCap[tier], next,
-                                          &d.d_status->n_overflow2, &d.d_status->malformed,
-                                          &d.d_status->hbm_next, last, st));
-      HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus),
-                                hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      n_list = tier < kHbmTiers - 1 ? d.h_status->n_overflow2 : 0;
-      std::swap(list, next);
-    }
-    HIP_TRY(c, hipEventRecord(d.e2, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipEventElapsedTime(&ms, d.e1, d.e2));
-    d.hbm_ms = ms;
-    d.malformed = d.h_status->malformed;  // (keys sent straight here report it)
+  r.n_ovf = direct ? (int32_t)n_jit : d.h_status->n_overflow;
+  d.n_hbm = r.n_ovf;
+  return 0;
+}
+
+// HBM-tier re-runs of the keys in d_ovf, each tier passing what outgrows it
+// to the next.
+int hbm_tiers(Run &r) {
+  if (r.n_ovf <= 0 || (r.flags & LC_FLAG_NO_HBM_RETRY)) return 0;
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  int32_t n_list = r.n_ovf;
+  int32_t *list = d.d_ovf.p, *next = d.d_ovf2.p;
+  HIP_TRY(c, hipEventRecord(d.e1, st));
+  // LC_HBM_COOP (test/A-B knob): 0 one wavefront per key throughout,
+  // 4 / 16 a workgroup of that many wavefronts per key throughout; default:
+  // 8 for at most 512 keys (two workgroups per CU), else 4.  (Round 1 used
+  // one wavefront per key beyond 4,096 keys; with the LDS tables the
+  // 4-wave workgroups win there too: version-less 10,000 x 1,000 at
+  // concurrency 20, HBM tier 128 -> 98 ms, tools/hbm_width_large.py.)
+  const char *coop_env = getenv("LC_HBM_COOP");
+  const int coop_mode = coop_env ? atoi(coop_env) : 1;
+  for (int tier = 0; tier < kHbmTiers && n_list > 0; tier++) {
+    int wpk = coop_mode == 1 ? (n_list <= kHbmCoop8MaxKeys ? 8 : 4) : coop_mode;
+    const bool coop = wpk == 4 || wpk == 8 || wpk == 16;
+    // workgroups: at most the resident ones (keys are claimed dynamically)
+    const int resident = wpk == 16 ? kHbmCoop16Resident : wpk == 8 ? 512
+                         : wpk == 4 ? kHbmCoop4Resident : kHbmWaves[tier];
+    const int waves = std::min<int>(std::min(kHbmWaves[tier], resident), n_list);
+    if (int rc = ensure(c, d.d_ws, lcdev::hbm_tier_ws_bytes(waves, kHbmCap[tier]))) return rc;
+    HIP_TRY(c, hipMemsetAsync(&d.d_status->n_overflow2, 0, sizeof(int32_t), st));
+    HIP_TRY(c, hipMemsetAsync(&d.d_status->hbm_next, 0, sizeof(int32_t), st));
+    const int last = tier == kHbmTiers - 1;
+    if (coop)
+      HIP_TRY(c, lcdev::launch_hbm_coop(r.d_ops, r.d_off, list, n_list, r.p, r.d_out, d.d_ws.p, waves,
+                                        kHbmCap[tier], next, &d.d_status->n_overflow2,
+                                        &d.d_status->malformed, &d.d_status->hbm_next, last, wpk, st));
+    else
+      HIP_TRY(c, lcdev::launch_hbm_tier(r.d_ops, r.d_off, list, n_list, r.p, r.d_out, d.d_ws.p, waves,
+                                        kHbmCap[tier], next, &d.d_status->n_overflow2,
+                                        &d.d_status->malformed, &d.d_status->hbm_next, last, st));
+    if (int e = read_status(c, d, st)) return e;
+    n_list = tier < kHbmTiers - 1 ? d.h_status->n_overflow2 : 0;
+    std::swap(list, next);
   }
-  HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
+  float ms = 0;
+  HIP_TRY(c, hipEventRecord(d.e2, st));
   HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, hipEventElapsedTime(&ms, d.e1, d.e2));
+  d.hbm_ms = ms;
+  d.malformed = d.h_status->malformed;  // (keys sent straight here report it)
+  return 0;
+}
+
+// The later tiers ran: d_status back to zero (the invariant between calls),
+// the call's totals.
+int end_call(Run &r) {
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), r.st));
+  HIP_TRY(c, hipStreamSynchronize(r.st));
   d.status_dirty = false;
-  if (timing) {
+  if (r.timing) {
     d.tot.timed_calls++;
     d.tot.fast_kernel_ms += d.fast_ms;
   }
   d.tot.kernel_ms += d.kernel_ms + d.hbm_ms;
   return 0;
+}
+
+// Run the tiers for n_keys keys whose device arrays are in place.
+int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
+               const lcdev::KParams &p, lc_key_result *d_out, hipStream_t st, int64_t flags,
+               const AuxOut &ao = AuxOut(), const Source &src = Source()) {
+  Run r{c, d, d_ops, d_off, n_keys, p, d_out, st, flags, ao, src};
+  r.fast_on = !(flags & LC_FLAG_NO_FAST_PATH);
+  r.gap_on = !(flags & (LC_FLAG_NO_FAST_PATH | LC_FLAG_NO_GAP_TIER));
+  r.want_wit = ao.wit && ao.kind;
+  r.signal = !src.chunks && r.fast_on && n_keys > 0;
+  r.timing = !r.signal || !(flags & LC_FLAG_NO_TIMING);
+  r.n_jit = n_keys;
+  if (int e = begin_call(r)) return e;
+  if (n_keys <= 0) return 0;
+  bool handed = false;
+  if (int e = first_pass(r, &handed)) return e;
+  if (handed)
+    if (int e = handoff(r)) return e;
+  if (r.n_jit == 0 && r.n_direct == 0) {  // every key decided
+    d.kernel_ms = d.fast_ms + d.gap_ms;
+    if (!d.timing_pending && r.timing) {
+      d.tot.timed_calls++;
+      d.tot.fast_kernel_ms += d.fast_ms;
+      d.tot.kernel_ms += d.kernel_ms;
+    }
+    // after a handoff d_status is not zero: cleared behind this call's work
+    // (the host has read it), not in front of the next call's
+    if (r.light) HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
+    d.status_dirty = false;
+    return 0;
+  }
+  if (int e = gap_tier(r)) return e;
+  if (int e = search_tier(r)) return e;
+  if (int e = hbm_tiers(r)) return e;
+  return end_call(r);
 }
 
 
@@ -1336,6 +1434,16 @@ bool irregular_sample(const Op *o, int64_t n) {
   return false;
 }
 
+// fn(k0, k1) over the keys [0, n_keys), cut into nth contiguous ranges with
+// a thread each (nth <= 1: on this thread).
+template <class F>
+void for_key_ranges(int64_t n_keys, int nth, F fn) {
+  if (nth <= 1) return fn(0, n_keys);
+  std::vector<std::thread> th;
+  for (int t = 0; t < nth; t++) th.emplace_back(fn, n_keys * t / nth, n_keys * (t + 1) / nth);
+  for (auto &x : th) x.join();
+}
+
 template <class Op>
 void plan_devices(const Op *ops, const int64_t *key_off, int64_t n_keys, int nd,
                   int64_t *bounds) {
@@ -1351,13 +1459,7 @@ void plan_devices(const Op *ops, const int64_t *key_off, int64_t n_keys, int nd,
     }
   };
   const int nth = any ? (int)std::min<int64_t>(16, std::max<int64_t>(1, n_keys >> 10)) : 1;
-  if (nth <= 1) {
-    price(0, n_keys);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; t++) th.emplace_back(price, n_keys * t / nth, n_keys * (t + 1) / nth);
-    for (auto &x : th) x.join();
-  }
+  for_key_ranges(n_keys, nth, price);
   for (int64_t k = 0; k < n_keys; k++) pre[(size_t)k + 1] += pre[(size_t)k];
   const double total = pre[(size_t)n_keys];
   bounds[0] = 0;
@@ -1377,6 +1479,84 @@ inline lc_op widen_op(const lc_op32 &o, int64_t base) {
                o.ret == LC_INF32 ? LC_INF : base + (int64_t)o.ret};
 }
 inline lc_op widen_op(const lc_op16 &o, int64_t base) { return widen_op(as32(o), base); }
+
+// The chunks of nk keys with offsets off[0..nk], records of rec_bytes:
+// contiguous key ranges of about kChunkBytes of input records, the last ones
+// halving down to kChunkTail (cut at key boundaries).  Fills ch.n, ch.k, ch.r.
+void plan_chunks(const int64_t *off, int64_t nk, size_t rec_bytes, Chunks &ch) {
+  const int64_t r0 = off[0];
+  const size_t in_bytes = rec_bytes * (size_t)(off[nk] - r0);
+  std::vector<size_t> sizes;  // from the end of the range
+  size_t sum = 0;
+  for (size_t left = in_bytes, want = kChunkTail; left > 0 && (int)sizes.size() < kMaxChunks - 1;) {
+    const size_t take = std::min(left, want);
+    sizes.push_back(take);
+    sum += take;
+    left -= take;
+    want = std::min(kChunkBytes, 2 * want);
+  }
+  ch.k.assign(1, 0);
+  int64_t rec_goal = (int64_t)((in_bytes - sum) / rec_bytes);  // records before the next cut
+  for (size_t i = sizes.size(); i-- > 1;) {
+    rec_goal += (int64_t)(sizes[i] / rec_bytes);
+    const int64_t k = std::lower_bound(off, off + nk, r0 + rec_goal) - off;
+    if (k > ch.k.back() && k < nk) ch.k.push_back(k);
+  }
+  ch.k.push_back(nk);
+  ch.n = (int)ch.k.size() - 1;
+  ch.r.clear();
+  for (int64_t k : ch.k) ch.r.push_back(off[k] - r0);
+}
+
+// A call's outputs back to the host: straight into the caller's buffers, or
+// (stage non-null) into the pinned buffer and copied out once the stream is
+// done.
+struct OutCopy {
+  void *to;
+  const void *from;
+  size_t bytes;
+};
+hipError_t copy_outputs(const OutCopy *oc, int n, hipStream_t st, char *stage) {
+  hipError_t e = hipSuccess;
+  size_t so = 0;
+  for (int i = 0; i < n && e == hipSuccess; i++) {
+    void *to = stage ? stage + so : oc[i].to;
+    so += up256(oc[i].bytes);
+    e = hipMemcpyAsync(to, oc[i].from, oc[i].bytes, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess || !stage) return e;
+  so = 0;
+  for (int i = 0; i < n; i++) {
+    std::memcpy(oc[i].to, stage + so, oc[i].bytes);
+    so += up256(oc[i].bytes);
+  }
+  return e;
+}
+
+// One device's counters of the call added to the context's (zeroed when the
+// call began).
+void fill_stats(lc_stats &s, const Dev &d) {
+  s.kernel_ms += d.kernel_ms;
+  s.fast_kernel_ms += d.fast_ms;
+  s.jit_kernel_ms += d.jit_ms;
+  s.n_jit_keys += d.n_jit;
+  s.gap_kernel_ms += d.gap_ms;
+  s.n_gap_keys += d.n_gap;
+  s.hbm_kernel_ms += d.hbm_ms;
+  s.n_hbm_keys += d.n_hbm;
+  s.n_malformed += d.malformed;
+}
+
+// LC_FLAG_WHOLE_GPU: the keys the tiers left :unknown at the configuration
+// budget, and those with more than LC_MAX_WINDOW ops open at once.
+void unknown_keys(const lc_key_result *res, int64_t n_keys, std::vector<int64_t> &budget,
+                  std::vector<int64_t> &window) {
+  for (int64_t k = 0; k < n_keys; k++)
+    if (res[k].verdict == LC_UNKNOWN && res[k].reason == LC_REASON_CONFIG_BUDGET) budget.push_back(k);
+    else if (res[k].verdict == LC_UNKNOWN && res[k].reason == LC_REASON_WINDOW_OVERFLOW)
+      window.push_back(k);
+}
 
 // lc_check_ex (48-byte lc_op) and lc_check32 (24-byte lc_op32, ABI 4) from
 // host memory: the keys split over the context's devices (plan_devices), one
@@ -1456,23 +1636,23 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
     const int64_t nrec = r1 - r0;
     const size_t ops_bytes = sizeof(lc_op) * (size_t)nrec;  // on the device: 48-byte records
     const size_t in_bytes = sizeof(Op) * (size_t)nrec;      // what crosses PCIe
-    int r = ensure(c, reinterpret_cast<char **>(&d.d_ops), &d.ops_cap, ops_bytes);
+    int r = ensure(c, d.d_ops, ops_bytes);
     // (the narrow records' staging: d_ops32, whichever width)
-    if (!r && narrow) r = ensure(c, reinterpret_cast<char **>(&d.d_ops32), &d.ops32_cap, in_bytes);
-    if (!r && narrow && key_base) r = ensure(c, &d.d_base, &d.base_cap, sizeof(int64_t) * (size_t)nk);
-    if (!r) r = ensure(c, &d.d_off, &d.off_cap, sizeof(int64_t) * (size_t)(nk + 1));
-    if (!r) r = ensure(c, &d.d_out, &d.out_cap, sizeof(lc_key_result) * (size_t)nk);
-    if (!r && want_wit) r = ensure(c, &d.d_wit, &d.wit_cap, sizeof(int32_t) * (size_t)nrec);
-    if (!r && want_wit) r = ensure(c, &d.d_kind, &d.kind_cap, sizeof(int32_t) * (size_t)nk);
-    if (!r && want_cert) r = ensure(c, &d.d_cert, &d.cert_cap, 4 * sizeof(int32_t) * (size_t)nk);
-    if (!r && want_cert) r = ensure(c, &d.d_cset, &d.cset_cap, sizeof(int32_t) * (size_t)nrec);
+    if (!r && narrow) r = ensure(c, d.d_ops32, in_bytes);
+    if (!r && narrow && key_base) r = ensure(c, d.d_base, sizeof(int64_t) * (size_t)nk);
+    if (!r) r = ensure(c, d.d_off, sizeof(int64_t) * (size_t)(nk + 1));
+    if (!r) r = ensure(c, d.d_out, sizeof(lc_key_result) * (size_t)nk);
+    if (!r && want_wit) r = ensure(c, d.d_wit, sizeof(int32_t) * (size_t)nrec);
+    if (!r && want_wit) r = ensure(c, d.d_kind, sizeof(int32_t) * (size_t)nk);
+    if (!r && want_cert) r = ensure(c, d.d_cert, 4 * sizeof(int32_t) * (size_t)nk);
+    if (!r && want_cert) r = ensure(c, d.d_cset, sizeof(int32_t) * (size_t)nrec);
     if (r) {
       rcs[di] = r;
       return;
     }
     // small pageable calls: inputs (offsets, bases, records) and outputs
     // (results, lc_aux arrays) through the pinned staging buffer
-    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+    auto up = up256;
     const bool pinned = is_pinned(c, ops + r0, in_bytes);
     const size_t off_bytes = sizeof(int64_t) * (size_t)(nk + 1);
     const size_t base_bytes = narrow && key_base ? sizeof(int64_t) * (size_t)nk : 0;
@@ -1483,7 +1663,7 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
     const size_t stage_need = up(off_bytes) + up(base_bytes) + up(in_bytes) + out_bytes;
     // (not with lc_aux outputs: the drop-in's C5 call with witnesses and
     // certificates measured 0.05-0.1 ms slower staged)
-    const bool stage = !pinned && !want_wit && !want_cert && stage_need <= kStageMax && !stage_off();
+    const bool stage = !pinned && !want_wit && !want_cert && stage_need <= kStageMax;
     if (stage && !stage_buf(c, d)) {
       rcs[di] = -ENOMEM;
       return;
@@ -1492,30 +1672,8 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
     char *st_base = stage ? st_off + up(off_bytes) : nullptr;
     char *st_ops = stage ? st_base + up(base_bytes) : nullptr;
     char *st_out = stage ? st_ops + up(in_bytes) : nullptr;
-    // chunks: contiguous key ranges of about kChunkBytes of input records,
-    // the last ones halving down to kChunkTail (cut at key boundaries)
     Chunks ch;
-    std::vector<size_t> sizes;  // from the end of the range
-    for (size_t left = in_bytes, want = kChunkTail; left > 0 && (int)sizes.size() < kMaxChunks - 1;) {
-      const size_t take = std::min(left, want);
-      sizes.push_back(take);
-      left -= take;
-      want = std::min(kChunkBytes, 2 * want);
-    }
-    ch.k.push_back(0);
-    {
-      size_t sum = 0;
-      for (size_t z : sizes) sum += z;
-      int64_t rec_goal = (int64_t)((in_bytes - sum) / sizeof(Op));  // records before the next cut
-      for (size_t i = sizes.size(); i-- > 1;) {
-        rec_goal += (int64_t)(sizes[i] / sizeof(Op));
-        int64_t k = std::lower_bound(key_off + a, key_off + b, r0 + rec_goal) - (key_off + a);
-        if (k > ch.k.back() && k < nk) ch.k.push_back(k);
-      }
-    }
-    ch.k.push_back(nk);
-    ch.n = (int)ch.k.size() - 1;
-    for (int64_t k : ch.k) ch.r.push_back(key_off[a + k] - r0);
+    plan_chunks(key_off + a, nk, sizeof(Op), ch);
     while ((int)d.cev.size() < ch.n) {
       hipEvent_t e = nullptr;
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
@@ -1527,11 +1685,11 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
     }
     ch.ready = d.cev.data();
     ch.max_len = max_len;
-    if (k32) ch.d_ops32 = static_cast<const lc_op32 *>(d.d_ops32);
-    if (k16) ch.d_ops16 = static_cast<const lc_op16 *>(d.d_ops32);
-    if (narrow) ch.d_base = key_base ? d.d_base : nullptr;
+    if (k32) ch.d_ops32 = reinterpret_cast<const lc_op32 *>(d.d_ops32.p);
+    if (k16) ch.d_ops16 = reinterpret_cast<const lc_op16 *>(d.d_ops32.p);
+    if (narrow) ch.d_base = key_base ? d.d_base.p : nullptr;
     nchunks[di] = ch.n;
-    char *dst = static_cast<char *>(narrow ? d.d_ops32 : d.d_ops);
+    char *dst = narrow ? d.d_ops32.p : reinterpret_cast<char *>(d.d_ops.p);
     const char *src = reinterpret_cast<const char *>(ops + r0);
     // the key offsets (and bases) lead; the compute stream waits for the
     // first chunk's event, which follows them on the copy stream
@@ -1544,9 +1702,9 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
       src_base = st_base;
     }
     if (e == hipSuccess)
-      e = hipMemcpyAsync(d.d_off, src_off, off_bytes, hipMemcpyHostToDevice, d.cst);
+      e = hipMemcpyAsync(d.d_off.p, src_off, off_bytes, hipMemcpyHostToDevice, d.cst);
     if (e == hipSuccess && base_bytes)
-      e = hipMemcpyAsync(d.d_base, src_base, base_bytes, hipMemcpyHostToDevice, d.cst);
+      e = hipMemcpyAsync(d.d_base.p, src_base, base_bytes, hipMemcpyHostToDevice, d.cst);
     if (e != hipSuccess) {
       set_err(c, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e));
       rcs[di] = -EIO;
@@ -1617,35 +1775,33 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
     d.last.h2d_bytes = (int64_t)(in_bytes + sizeof(int64_t) * (size_t)(nk + 1) +
                                  (narrow && key_base ? sizeof(int64_t) * (size_t)nk : 0));
     d.last.pinned = pinned;
-    WitOut wo;
-    wo.n_records = nrec;
+    AuxOut ao;
+    ao.n_records = nrec;
     if (want_wit) {
-      wo.wit = d.d_wit;
-      wo.kind = d.d_kind;
+      ao.wit = d.d_wit.p;
+      ao.kind = d.d_kind.p;
     }
     if (want_cert) {
-      wo.cert = d.d_cert;
-      wo.cset = d.d_cset;
+      ao.cert = d.d_cert.p;
+      ao.cset = d.d_cset.p;
     }
-    wo.h_off = key_off + a;
-    wo.chunks = &ch;
-    if (k32 && !want_wit && !want_cert && !(flags & LC_FLAG_NO_FAST_PATH) && !native32_off()) {
+    Source from;
+    from.h_off = key_off + a;
+    from.chunks = &ch;
+    if (k32 && !want_wit && !want_cert && !(flags & LC_FLAG_NO_FAST_PATH)) {
       // decided from the 24-byte records; widened only if a key is handed over
-      wo.ops32 = static_cast<const lc_op32 *>(d.d_ops32);
-      wo.base32 = key_base ? d.d_base : nullptr;
-      wo.widen = [&](const lc_op **out) -> int {
-        HIP_TRY(c, lcdev::launch_widen32(static_cast<const lc_op32 *>(d.d_ops32), d.d_off,
-                                         key_base ? d.d_base : nullptr, nk, max_len,
-                                         static_cast<lc_op *>(d.d_ops), d.stream));
-        *out = static_cast<const lc_op *>(d.d_ops);
+      from.ops32 = ch.d_ops32;
+      from.base32 = ch.d_base;
+      from.widen = [&](const lc_op **out) -> int {
+        HIP_TRY(c, lcdev::launch_widen32(ch.d_ops32, d.d_off.p, ch.d_base, nk, max_len, d.d_ops.p,
+                                         d.stream));
+        *out = d.d_ops.p;
         return 0;
       };
     }
-    r = run_device(c, d, static_cast<const lc_op *>(d.d_ops), d.d_off, nk, p, d.d_out, d.stream,
-                   flags, wo);
+    r = run_device(c, d, d.d_ops.p, d.d_off.p, nk, p, d.d_out.p, d.stream, flags, ao, from);
     join_helper();
-    if (!r) r = run_certificates(c, d, static_cast<const lc_op *>(d.d_ops), d.d_off, nk, p,
-                                 d.d_out, d.stream, wo);
+    if (!r) r = run_certificates(c, d, d.d_ops.p, d.d_off.p, nk, p, d.d_out.p, d.stream, ao);
     if (r) {
       // the copy stream may still read the caller's buffer
       (void)hipStreamSynchronize(d.cst);
@@ -1653,35 +1809,15 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
       rcs[di] = r;
       return;
     }
-    // outputs: straight into the caller's buffers, or (staged) into the
-    // pinned buffer and copied out once the stream is done
-    struct OutCopy {
-      void *to;
-      const void *from;
-      size_t bytes;
-    };
     OutCopy oc[5];
     int n_oc = 0;
-    oc[n_oc++] = {out + a, d.d_out, sizeof(lc_key_result) * (size_t)nk};
-    if (want_wit && nrec) oc[n_oc++] = {aux->witness + r0, d.d_wit, sizeof(int32_t) * (size_t)nrec};
-    if (want_wit) oc[n_oc++] = {aux->witness_kind + a, d.d_kind, sizeof(int32_t) * (size_t)nk};
-    if (want_cert) oc[n_oc++] = {aux->certificate + 4 * a, d.d_cert, 4 * sizeof(int32_t) * (size_t)nk};
+    oc[n_oc++] = {out + a, d.d_out.p, sizeof(lc_key_result) * (size_t)nk};
+    if (want_wit && nrec) oc[n_oc++] = {aux->witness + r0, d.d_wit.p, sizeof(int32_t) * (size_t)nrec};
+    if (want_wit) oc[n_oc++] = {aux->witness_kind + a, d.d_kind.p, sizeof(int32_t) * (size_t)nk};
+    if (want_cert) oc[n_oc++] = {aux->certificate + 4 * a, d.d_cert.p, 4 * sizeof(int32_t) * (size_t)nk};
     if (want_cert && aux->certificate_set && nrec)
-      oc[n_oc++] = {aux->certificate_set + r0, d.d_cset, sizeof(int32_t) * (size_t)nrec};
-    size_t so = 0;
-    for (int i = 0; i < n_oc && e == hipSuccess; i++) {
-      void *to = stage ? st_out + so : oc[i].to;
-      so += up(oc[i].bytes);
-      e = hipMemcpyAsync(to, oc[i].from, oc[i].bytes, hipMemcpyDeviceToHost, d.stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-    if (e == hipSuccess && stage) {
-      so = 0;
-      for (int i = 0; i < n_oc; i++) {
-        std::memcpy(oc[i].to, st_out + so, oc[i].bytes);
-        so += up(oc[i].bytes);
-      }
-    }
+      oc[n_oc++] = {aux->certificate_set + r0, d.d_cset.p, sizeof(int32_t) * (size_t)nrec};
+    e = copy_outputs(oc, n_oc, d.stream, st_out);
     if (e != hipSuccess) {
       set_err(c, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e));
       rcs[di] = -EIO;
@@ -1711,15 +1847,7 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
   for (int di = 0; di < nd; di++) {
     const Dev &d = c->devs[di];
     if (rcs[di] && !rc) rc = rcs[di];
-    c->stats.kernel_ms += d.kernel_ms;
-    c->stats.fast_kernel_ms += d.fast_ms;
-    c->stats.jit_kernel_ms += d.jit_ms;
-    c->stats.n_jit_keys += d.n_jit;
-    c->stats.gap_kernel_ms += d.gap_ms;
-    c->stats.n_gap_keys += d.n_gap;
-    c->stats.hbm_kernel_ms += d.hbm_ms;
-    c->stats.n_hbm_keys += d.n_hbm;
-    c->stats.n_malformed += d.malformed;
+    fill_stats(c->stats, d);
     c->prof.first_start_ms = std::min(c->prof.first_start_ms, d.t_start);
     c->prof.last_start_ms = std::max(c->prof.last_start_ms, d.t_start);
     c->prof.first_end_ms = std::min(c->prof.first_end_ms, d.t_end);
@@ -1729,10 +1857,7 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
   c->prof.joined_ms = since();
   if (!rc && (flags & LC_FLAG_WHOLE_GPU)) {
     std::vector<int64_t> todo, todo_w;
-    for (int64_t k = 0; k < n_keys; k++)
-      if (out[k].verdict == LC_UNKNOWN && out[k].reason == LC_REASON_CONFIG_BUDGET) todo.push_back(k);
-      else if (out[k].verdict == LC_UNKNOWN && out[k].reason == LC_REASON_WINDOW_OVERFLOW)
-        todo_w.push_back(k);
+    unknown_keys(out, n_keys, todo, todo_w);
     auto fetch = [&](int64_t k, std::vector<lc_op> &v) {
       v.resize((size_t)(key_off[k + 1] - key_off[k]));
       const int64_t base = key_base ? key_base[k] : 0;
@@ -1757,6 +1882,155 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
   c->stats.total_ms = since();
   c->prof.total_ms = c->stats.total_ms;
   c->prof.n_devices = nd;
+  return rc;
+}
+
+// key_off[n_keys] - key_off[0] of key offsets that live in device memory,
+// read through d.h_status (pinned).  Only before any status copy of the
+// same call: ahead of run_device, or from Source::widen at the handoff,
+// which precedes the handoff's status read.
+int device_record_count(lc_ctx *c, Dev &d, const int64_t *d_key_off, int64_t n_keys, hipStream_t st,
+                        int64_t *nrec) {
+  int64_t *ends = reinterpret_cast<int64_t *>(d.h_status);
+  HIP_TRY(c, hipMemcpyAsync(&ends[0], d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&ends[1], d_key_off + n_keys, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  *nrec = ends[1] - ends[0];
+  return 0;
+}
+
+// lc_check_device32: the 24-byte records in device memory widened into
+// d.d_ops, *nrec of them.
+int widen_device32(lc_ctx *c, Dev &d, const lc_op32 *d_ops32, const int64_t *d_key_off,
+                   const int64_t *d_key_base, int64_t n_keys, hipStream_t st, int64_t *nrec) {
+  if (int e = device_record_count(c, d, d_key_off, n_keys, st, nrec)) return e;
+  if (*nrec < 0) {
+    set_err(c, "lc_check_device32: key_off[n_keys] < key_off[0]");
+    return -EINVAL;
+  }
+  if (int e = ensure(c, d.d_ops, sizeof(lc_op) * (size_t)*nrec)) return e;
+  // the grid's second dimension for long keys: sized from the mean length
+  // (any size is correct: each workgroup strides its key)
+  HIP_TRY(c, lcdev::launch_widen32(d_ops32, d_key_off, d_key_base, n_keys, 4 * (*nrec / n_keys + 1),
+                                   d.d_ops.p, st));
+  return 0;
+}
+
+// LC_FLAG_WHOLE_GPU after a device call: the results and the keys' records
+// are in device memory: read back the verdicts, and each key the frontier
+// exchange takes.  d_cert: the call's certificates (null: none wanted).
+int whole_gpu_device(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off, int64_t n_keys,
+                     const lc_opts *opts, lc_key_result *d_out, int32_t *d_cert, hipStream_t st) {
+  std::vector<lc_key_result> res((size_t)n_keys);
+  int64_t base = 0;
+  HIP_TRY(c, hipMemcpyAsync(res.data(), d_out, sizeof(lc_key_result) * (size_t)n_keys,
+                            hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&base, d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  std::vector<int64_t> todo, todo_w;
+  unknown_keys(res.data(), n_keys, todo, todo_w);
+  auto fetch = [&](int64_t k, std::vector<lc_op> &v) {
+    int64_t se[2];
+    if (hipMemcpy(se, d_key_off + k, sizeof se, hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+    v.resize((size_t)(se[1] - se[0]));
+    if (!v.empty() && hipMemcpy(v.data(), d_ops + (se[0] - base), sizeof(lc_op) * v.size(),
+                                hipMemcpyDeviceToHost) != hipSuccess)
+      return -EIO;
+    return 0;
+  };
+  auto store = [&](int64_t k, const lc_key_result &r) {
+    if (d_cert) {
+      const int32_t none[4] = {LC_CERT_NONE, -1, -1, 0};
+      if (hipMemcpy(d_cert + 4 * k, none, sizeof none, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+    }
+    return hipMemcpy(d_out + k, &r, sizeof r, hipMemcpyHostToDevice) == hipSuccess ? 0 : -EIO;
+  };
+  int rc = whole_gpu(c, todo, opts, fetch, store);
+  if (!rc) rc = whole_gpu(c, todo_w, opts, fetch, store);
+  return rc;
+}
+
+// lc_check_device_ex (48-byte records) and lc_check_device32 (rec32: 24-byte
+// records and key bases), on the context's first device.  `who` names the
+// entry point in its errors.
+// Hot paths: a call without lc_aux outputs or LC_FLAG_WHOLE_GPU issues
+// hipSetDevice and then run_device's calls, nothing else; 24-byte records
+// are decided as they are (Source::ops32) and widened only at a handoff.
+int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const int64_t *d_key_off,
+                 const int64_t *d_key_base, int64_t n_keys, const lc_opts *opts, lc_key_result *d_out,
+                 void *stream, const lc_aux *aux) {
+  const auto t0 = std::chrono::steady_clock::now();
+  c->stats = lc_stats{};
+  if (n_keys < 0 || (n_keys > 0 && (!ops || !d_key_off || !d_out))) {
+    set_err(c, std::string(who) + ": null buffer or negative n_keys");
+    return -EINVAL;
+  }
+  const unsigned align = rec32 ? 8 : 16;
+  if (reinterpret_cast<uintptr_t>(ops) % align) {
+    set_err(c, std::string(who) + ": ops must be " + std::to_string(align) + "-byte aligned");
+    return -EINVAL;
+  }
+  lcdev::KParams p;
+  int rc = opts_to_params(c, opts, &p);
+  if (rc) return rc;
+  Dev &d = c->devs[0];
+  HIP_TRY(c, hipSetDevice(d.id));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : d.stream;
+  const int64_t flags = opts ? opts->flags : 0;
+  const bool want_wit = aux && aux->witness && aux->witness_kind;
+  const bool want_cert = aux && aux->certificate;
+  const lc_op32 *d_ops32 = rec32 ? static_cast<const lc_op32 *>(ops) : nullptr;
+  // d_ops points at the record of index d_key_off[0]; the kernels read that
+  // base themselves, so a key_off slice of a larger array may be passed.
+  const lc_op *d_ops = rec32 ? nullptr : static_cast<const lc_op *>(ops);
+  AuxOut ao;
+  Source src;
+  if (rec32 && n_keys > 0 && !(aux && (aux->witness || aux->certificate)) &&
+      !(flags & (LC_FLAG_NO_FAST_PATH | LC_FLAG_WHOLE_GPU))) {
+    // decided from the 24-byte records as they are; the 48-byte form (and
+    // the record count it needs, read from device memory) only if a key is
+    // handed over to the later tiers
+    src.ops32 = d_ops32;
+    src.base32 = d_key_base;
+    src.widen = [&](const lc_op **out) -> int {
+      int64_t nrec = 0;
+      if (int e = widen_device32(c, d, d_ops32, d_key_off, d_key_base, n_keys, st, &nrec)) return e;
+      *out = d.d_ops.p;
+      return 0;
+    };
+  } else if (n_keys > 0) {
+    // the record count lives in device memory
+    if (rec32) {
+      if (int e = widen_device32(c, d, d_ops32, d_key_off, d_key_base, n_keys, st, &ao.n_records))
+        return e;
+      d_ops = d.d_ops.p;
+    } else if (want_wit || want_cert) {
+      if (int e = device_record_count(c, d, d_key_off, n_keys, st, &ao.n_records)) return e;
+    }
+    if (want_wit) {
+      ao.wit = aux->witness;
+      ao.kind = aux->witness_kind;
+    }
+    if (want_cert) {
+      ao.cert = aux->certificate;
+      ao.cset = aux->certificate_set;
+      if (!ao.cset) {  // the position sets still need a home on the device
+        if (int e = ensure(c, d.d_cset, sizeof(int32_t) * (size_t)ao.n_records)) return e;
+        ao.cset = d.d_cset.p;
+      }
+    }
+  }
+  rc = run_device(c, d, d_ops, d_key_off, n_keys, p, d_out, st, flags, ao, src);
+  if (!rc) rc = run_certificates(c, d, d_ops, d_key_off, n_keys, p, d_out, st, ao);
+  if (!rc && (flags & LC_FLAG_WHOLE_GPU) && n_keys > 0)
+    rc = whole_gpu_device(c, d_ops, d_key_off, n_keys, opts, d_out, want_cert ? aux->certificate : nullptr,
+                          st);
+  fill_stats(c->stats, d);
+  c->stats.n_keys = n_keys;
+  c->stats.n_ops = -1;  // not read back from device memory
+  c->stats.n_devices = 1;
+  c->stats.total_ms = std::chrono::duration<double, std::milli>(
+                          std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
 
@@ -1795,19 +2069,12 @@ int lc_open(uint32_t device_mask, lc_ctx **out) {
     for (int v = 0; v < (virt >= 2 ? virt : 1); v++) {
       Dev d;
       d.id = i;
-      if (hipSetDevice(i) != hipSuccess ||
-          hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking) != hipSuccess ||
-          hipStreamCreateWithFlags(&d.cst, hipStreamNonBlocking) != hipSuccess ||
-          hipStreamCreateWithFlags(&d.cst2, hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&d.e0, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.e1, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.e2, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.ef, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.eg, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.el, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.eh0, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.eh1, kEventFlags) != hipSuccess ||
-          hipEventCreateWithFlags(&d.es, kEventFlags) != hipSuccess ||
+      bool ok = hipSetDevice(i) == hipSuccess;
+      for (hipStream_t *s : {&d.stream, &d.cst, &d.cst2})
+        ok = ok && hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess;
+      for (hipEvent_t *e : {&d.e0, &d.e1, &d.e2, &d.ef, &d.eg, &d.el, &d.eh0, &d.eh1, &d.es})
+        ok = ok && hipEventCreateWithFlags(e, kEventFlags) == hipSuccess;
+      if (!ok ||
           hipMalloc(reinterpret_cast<void **>(&d.d_status), sizeof(lcdev::KStatus)) != hipSuccess ||
           hipHostMalloc(reinterpret_cast<void **>(&d.h_status), sizeof(lcdev::KStatus), 0) != hipSuccess ||
           hipHostMalloc(reinterpret_cast<void **>(&d.h_handoff), 2 * sizeof(int32_t),
@@ -1849,36 +2116,19 @@ void lc_close(lc_ctx *c) {
     if (d.res_d) (void)hipFree(d.res_d);
     if (d.res_h) (void)hipHostFree(d.res_h);
     if (d.stream) (void)hipStreamSynchronize(d.stream);
-    if (d.d_ops) (void)hipFree(d.d_ops);
-    if (d.d_off) (void)hipFree(d.d_off);
-    if (d.d_out) (void)hipFree(d.d_out);
-    if (d.d_ovf) (void)hipFree(d.d_ovf);
-    if (d.d_ovf2) (void)hipFree(d.d_ovf2);
-    if (d.d_ws) (void)hipFree(d.d_ws);
+    // every Buf of Dev
+    for (void *b : std::initializer_list<void *>{
+             d.d_ops.p, d.d_off.p, d.d_out.p, d.d_ovf.p, d.d_ovf2.p, d.d_jit.p, d.d_flags.p, d.d_jit2.p,
+             d.d_gap2.p, d.d_gws.p, d.d_cex.p, d.d_ws.p, d.d_wit.p, d.d_kind.p, d.d_cert.p, d.d_cset.p,
+             d.d_cws.p, d.d_ops32.p, d.d_base.p})
+      if (b) (void)hipFree(b);
     if (d.d_status) (void)hipFree(d.d_status);
     if (d.h_status) (void)hipHostFree(d.h_status);
     if (d.h_handoff) (void)hipHostFree(d.h_handoff);
     if (d.h_done) (void)hipHostFree(d.h_done);
     if (d.h_stage) (void)hipHostFree(d.h_stage);
-    if (d.e0) (void)hipEventDestroy(d.e0);
-    if (d.e1) (void)hipEventDestroy(d.e1);
-    if (d.e2) (void)hipEventDestroy(d.e2);
-    if (d.ef) (void)hipEventDestroy(d.ef);
-    for (hipEvent_t e : {d.eg, d.el, d.eh0, d.eh1, d.es})
+    for (hipEvent_t e : {d.e0, d.e1, d.e2, d.ef, d.eg, d.el, d.eh0, d.eh1, d.es})
       if (e) (void)hipEventDestroy(e);
-    if (d.d_jit) (void)hipFree(d.d_jit);
-    if (d.d_jit2) (void)hipFree(d.d_jit2);
-    if (d.d_flags) (void)hipFree(d.d_flags);
-    if (d.d_gws) (void)hipFree(d.d_gws);
-    if (d.d_cex) (void)hipFree(d.d_cex);
-    if (d.d_wit) (void)hipFree(d.d_wit);
-    if (d.d_kind) (void)hipFree(d.d_kind);
-    if (d.d_cert) (void)hipFree(d.d_cert);
-    if (d.d_cset) (void)hipFree(d.d_cset);
-    if (d.d_cws) (void)hipFree(d.d_cws);
-    if (d.d_gap2) (void)hipFree(d.d_gap2);
-    if (d.d_ops32) (void)hipFree(d.d_ops32);
-    if (d.d_base) (void)hipFree(d.d_base);
     for (hipEvent_t e : d.cev) (void)hipEventDestroy(e);
     for (hipStream_t cs : {d.cst, d.cst2})
       if (cs) {
@@ -2004,14 +2254,7 @@ int lc_plan_partition(const lc_op *ops, const int64_t *key_off, int64_t n_keys,
       pre[(size_t)k + 1] = ops ? key_cost(ops + key_off[k], n) : (double)n + 64.0;
     }
   };
-  if (nth <= 1) {
-    price(0, n_keys);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; t++)
-      th.emplace_back(price, n_keys * t / nth, n_keys * (t + 1) / nth);
-    for (auto &x : th) x.join();
-  }
+  for_key_ranges(n_keys, nth, price);
   for (int64_t k = 0; k < n_keys; k++) pre[(size_t)k + 1] += pre[(size_t)k];
   const double total = pre[(size_t)n_keys];
   bounds[0] = 0;
@@ -2066,101 +2309,8 @@ int lc_check_device_ex(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off,
                        int64_t n_keys, const lc_opts *opts, lc_key_result *d_out,
                        void *stream, const lc_aux *aux) {
   if (!c) return -EINVAL;
-  const auto t0 = std::chrono::steady_clock::now();
-  c->stats = lc_stats{};
-  if (n_keys < 0 || (n_keys > 0 && (!d_ops || !d_key_off || !d_out))) {
-    set_err(c, "lc_check_device: null buffer or negative n_keys");
-    return -EINVAL;
-  }
-  if (reinterpret_cast<uintptr_t>(d_ops) % 16) {
-    set_err(c, "lc_check_device: ops must be 16-byte aligned");
-    return -EINVAL;
-  }
-  lcdev::KParams p;
-  int rc = opts_to_params(c, opts, &p);
-  if (rc) return rc;
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : d.stream;
-  WitOut wo;
-  const bool want_wit = aux && aux->witness && aux->witness_kind;
-  const bool want_cert = aux && aux->certificate;
-  if ((want_wit || want_cert) && n_keys > 0) {
-    // the record count lives in device memory: key_off[n_keys] - key_off[0]
-    int64_t ends[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(&ends[0], d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&ends[1], d_key_off + n_keys, sizeof(int64_t), hipMemcpyDeviceToHost,
-                              st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    wo.n_records = ends[1] - ends[0];
-    if (want_wit) {
-      wo.wit = aux->witness;
-      wo.kind = aux->witness_kind;
-    }
-    if (want_cert) {
-      wo.cert = aux->certificate;
-      wo.cset = aux->certificate_set;
-      if (!wo.cset) {  // the position sets still need a home on the device
-        if (int e = ensure(c, &d.d_cset, &d.cset_cap, sizeof(int32_t) * (size_t)wo.n_records))
-          return e;
-        wo.cset = d.d_cset;
-      }
-    }
-  }
-  // d_ops points at the record of index d_key_off[0]; the kernels read that
-  // base themselves, so a key_off slice of a larger array may be passed.
-  rc = run_device(c, d, d_ops, d_key_off, n_keys, p, d_out, st,
-                  opts ? opts->flags : 0, wo);
-  if (!rc) rc = run_certificates(c, d, d_ops, d_key_off, n_keys, p, d_out, st, wo);
-  if (!rc && opts && (opts->flags & LC_FLAG_WHOLE_GPU) && n_keys > 0) {
-    // the results and the keys' records are in device memory: read back the
-    // verdicts, and each key the frontier exchange takes
-    std::vector<lc_key_result> res((size_t)n_keys);
-    int64_t base = 0;
-    HIP_TRY(c, hipMemcpyAsync(res.data(), d_out, sizeof(lc_key_result) * (size_t)n_keys,
-                              hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(&base, d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    std::vector<int64_t> todo, todo_w;
-    for (int64_t k = 0; k < n_keys; k++)
-      if (res[k].verdict == LC_UNKNOWN && res[k].reason == LC_REASON_CONFIG_BUDGET) todo.push_back(k);
-      else if (res[k].verdict == LC_UNKNOWN && res[k].reason == LC_REASON_WINDOW_OVERFLOW)
-        todo_w.push_back(k);
-    auto fetch = [&](int64_t k, std::vector<lc_op> &v) {
-      int64_t se[2];
-      if (hipMemcpy(se, d_key_off + k, sizeof se, hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
-      v.resize((size_t)(se[1] - se[0]));
-      if (!v.empty() && hipMemcpy(v.data(), d_ops + (se[0] - base), sizeof(lc_op) * v.size(),
-                                  hipMemcpyDeviceToHost) != hipSuccess)
-        return -EIO;
-      return 0;
-    };
-    auto store = [&](int64_t k, const lc_key_result &r) {
-      if (want_cert) {
-        const int32_t none[4] = {LC_CERT_NONE, -1, -1, 0};
-        if (hipMemcpy(aux->certificate + 4 * k, none, sizeof none, hipMemcpyHostToDevice) != hipSuccess)
-          return -EIO;
-      }
-      return hipMemcpy(d_out + k, &r, sizeof r, hipMemcpyHostToDevice) == hipSuccess ? 0 : -EIO;
-    };
-    rc = whole_gpu(c, todo, opts, fetch, store);
-    if (!rc) rc = whole_gpu(c, todo_w, opts, fetch, store);
-  }
-  c->stats.kernel_ms = d.kernel_ms;
-  c->stats.fast_kernel_ms = d.fast_ms;
-  c->stats.jit_kernel_ms = d.jit_ms;
-  c->stats.n_jit_keys = d.n_jit;
-  c->stats.gap_kernel_ms = d.gap_ms;
-  c->stats.n_gap_keys = d.n_gap;
-  c->stats.hbm_kernel_ms = d.hbm_ms;
-  c->stats.n_hbm_keys = d.n_hbm;
-  c->stats.n_malformed = d.malformed;
-  c->stats.n_keys = n_keys;
-  c->stats.n_ops = -1;  // not read back from device memory
-  c->stats.n_devices = 1;
-  c->stats.total_ms = std::chrono::duration<double, std::milli>(
-                          std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return check_device(c, "lc_check_device", d_ops, false, d_key_off, nullptr, n_keys, opts, d_out,
+                      stream, aux);
 }
 
 int lc_check_device(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off,
@@ -2169,90 +2319,12 @@ int lc_check_device(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off,
   return lc_check_device_ex(c, d_ops, d_key_off, n_keys, opts, d_out, stream, nullptr);
 }
 
-
 int lc_check_device32(lc_ctx *c, const lc_op32 *d_ops, const int64_t *d_key_off,
                       const int64_t *d_key_base, int64_t n_keys, const lc_opts *opts,
                       lc_key_result *d_out, void *stream, const lc_aux *aux) {
   if (!c) return -EINVAL;
-  if (n_keys < 0 || (n_keys > 0 && (!d_ops || !d_key_off || !d_out))) {
-    set_err(c, "lc_check_device32: null buffer or negative n_keys");
-    return -EINVAL;
-  }
-  if (reinterpret_cast<uintptr_t>(d_ops) % 8) {
-    set_err(c, "lc_check_device32: ops must be 8-byte aligned");
-    return -EINVAL;
-  }
-  if (n_keys == 0) return lc_check_device_ex(c, nullptr, d_key_off, 0, opts, d_out, stream, aux);
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : d.stream;
-  const int64_t flags = opts ? opts->flags : 0;
-  if (!(aux && (aux->witness || aux->certificate)) &&
-      !(flags & (LC_FLAG_NO_FAST_PATH | LC_FLAG_WHOLE_GPU)) && !native32_off()) {
-    // decided from the 24-byte records as they are; the 48-byte form (and
-    // the record count it needs, read from device memory) only if a key is
-    // handed over to the later tiers
-    lcdev::KParams p;
-    if (int rc = opts_to_params(c, opts, &p)) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    c->stats = lc_stats{};
-    WitOut wo;
-    wo.ops32 = d_ops;
-    wo.base32 = d_key_base;
-    wo.widen = [&](const lc_op **out) -> int {
-      int64_t *ends = reinterpret_cast<int64_t *>(d.h_status);  // (pinned; read before any later status copy)
-      HIP_TRY(c, hipMemcpyAsync(&ends[0], d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(&ends[1], d_key_off + n_keys, sizeof(int64_t), hipMemcpyDeviceToHost,
-                                st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      const int64_t nrec = ends[1] - ends[0];
-      if (nrec < 0) {
-        set_err(c, "lc_check_device32: key_off[n_keys] < key_off[0]");
-        return -EINVAL;
-      }
-      if (int e = ensure(c, reinterpret_cast<char **>(&d.d_ops), &d.ops_cap,
-                         sizeof(lc_op) * (size_t)std::max<int64_t>(nrec, 1)))
-        return e;
-      HIP_TRY(c, lcdev::launch_widen32(d_ops, d_key_off, d_key_base, n_keys, 4 * (nrec / n_keys + 1),
-                                       static_cast<lc_op *>(d.d_ops), st));
-      *out = static_cast<const lc_op *>(d.d_ops);
-      return 0;
-    };
-    int rc = run_device(c, d, nullptr, d_key_off, n_keys, p, d_out, st, flags, wo);
-    c->stats.kernel_ms = d.kernel_ms;
-    c->stats.fast_kernel_ms = d.fast_ms;
-    c->stats.jit_kernel_ms = d.jit_ms;
-    c->stats.n_jit_keys = d.n_jit;
-    c->stats.gap_kernel_ms = d.gap_ms;
-    c->stats.n_gap_keys = d.n_gap;
-    c->stats.hbm_kernel_ms = d.hbm_ms;
-    c->stats.n_hbm_keys = d.n_hbm;
-    c->stats.n_malformed = d.malformed;
-    c->stats.n_keys = n_keys;
-    c->stats.n_ops = -1;
-    c->stats.n_devices = 1;
-    c->stats.total_ms = std::chrono::duration<double, std::milli>(
-                            std::chrono::steady_clock::now() - t0).count();
-    return rc;
-  }
-  // the record count lives in device memory: key_off[n_keys] - key_off[0]
-  int64_t *ends = reinterpret_cast<int64_t *>(d.h_status);  // (pinned; free between calls)
-  HIP_TRY(c, hipMemcpyAsync(&ends[0], d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(&ends[1], d_key_off + n_keys, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  const int64_t nrec = ends[1] - ends[0];
-  if (nrec < 0) {
-    set_err(c, "lc_check_device32: key_off[n_keys] < key_off[0]");
-    return -EINVAL;
-  }
-  if (int e = ensure(c, reinterpret_cast<char **>(&d.d_ops), &d.ops_cap, sizeof(lc_op) * (size_t)nrec))
-    return e;
-  // the grid's second dimension for long keys: sized from the mean length
-  // (any size is correct: each workgroup strides its key)
-  HIP_TRY(c, lcdev::launch_widen32(d_ops, d_key_off, d_key_base, n_keys, 4 * (nrec / n_keys + 1),
-                                   static_cast<lc_op *>(d.d_ops), st));
-  return lc_check_device_ex(c, static_cast<const lc_op *>(d.d_ops), d_key_off, n_keys, opts, d_out,
-                            stream, aux);
+  return check_device(c, "lc_check_device32", d_ops, true, d_key_off, d_key_base, n_keys, opts, d_out,
+                      stream, aux);
 }
 
 int lc_check_frontiers(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
@@ -2283,24 +2355,25 @@ int lc_check_frontiers(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int6
   const size_t cfg_bytes = sizeof(lc_fx_config) * (size_t)max_per_key * (size_t)n_keys;
   // scratch: the records, offsets, stops and results share the context's
   // lc_check buffers (a context is not re-entrant)
-  int e = ensure(c, reinterpret_cast<char **>(&d.d_ops), &d.ops_cap, sizeof(lc_op) * (size_t)nrec);
-  if (!e) e = ensure(c, &d.d_off, &d.off_cap, sizeof(int64_t) * (size_t)(2 * n_keys + 1));
-  if (!e) e = ensure(c, reinterpret_cast<char **>(&d.d_gws), &d.gws_cap, cfg_bytes);
-  if (!e) e = ensure(c, &d.d_jit, &d.jit_cap, sizeof(int32_t) * (size_t)n_keys);
-  if (!e) e = ensure(c, &d.d_jit2, &d.jit2_cap, sizeof(int32_t) * (size_t)n_keys);
+  int e = ensure(c, d.d_ops, sizeof(lc_op) * (size_t)nrec);
+  if (!e) e = ensure(c, d.d_off, sizeof(int64_t) * (size_t)(2 * n_keys + 1));
+  if (!e) e = ensure(c, d.d_gws, cfg_bytes);
+  if (!e) e = ensure(c, d.d_jit, sizeof(int32_t) * (size_t)n_keys);
+  if (!e) e = ensure(c, d.d_jit2, sizeof(int32_t) * (size_t)n_keys);
   if (e) return e;
-  int64_t *d_stop = d.d_off + (n_keys + 1);
-  lc_fx_config *d_cfg = reinterpret_cast<lc_fx_config *>(d.d_gws);
-  const lc_op *d_ops = static_cast<const lc_op *>(d.d_ops);
+  int64_t *d_off = d.d_off.p, *d_stop = d_off + (n_keys + 1);
+  int32_t *d_n = d.d_jit.p, *d_retry = d.d_jit2.p;
+  lc_fx_config *d_cfg = reinterpret_cast<lc_fx_config *>(d.d_gws.p);
+  const lc_op *d_ops = d.d_ops.p;
   hipStream_t st = d.stream;
   // the inputs: through the staging buffer when pageable and small (as lc_check's)
   const void *src_ops = ops + r0, *src_off = key_off, *src_stop = stop_op;
   const size_t ops_b = sizeof(lc_op) * (size_t)nrec, off_b = sizeof(int64_t) * (size_t)(n_keys + 1),
                stop_b = sizeof(int64_t) * (size_t)n_keys;
-  if (ops_b + off_b + stop_b + 512 <= kStageMax && !stage_off() && !is_pinned(c, ops + r0, ops_b)) {
+  if (ops_b + off_b + stop_b + 512 <= kStageMax && !is_pinned(c, ops + r0, ops_b)) {
     char *sb = stage_buf(c, d);
     if (!sb) return -ENOMEM;
-    char *so = sb, *sf = so + ((ops_b + 255) & ~size_t(255)), *ss = sf + ((off_b + 255) & ~size_t(255));
+    char *so = sb, *sf = so + up256(ops_b), *ss = sf + up256(off_b);
     std::memcpy(so, src_ops, ops_b);
     std::memcpy(sf, src_off, off_b);
     std::memcpy(ss, src_stop, stop_b);
@@ -2308,29 +2381,25 @@ int lc_check_frontiers(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int6
     src_off = sf;
     src_stop = ss;
   }
-  HIP_TRY(c, hipMemcpyAsync(d.d_ops, src_ops, ops_b, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(d.d_off, src_off, off_b, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d.d_ops.p, src_ops, ops_b, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_off, src_off, off_b, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_stop, src_stop, stop_b, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
   d.status_dirty = true;
-  HIP_TRY(c, lcdev::launch_frontier_dump(d_ops, d.d_off, d_stop, n_keys, p, d_cfg, max_per_key, d.d_jit,
-                                         d.d_jit2, &d.d_status->n_overflow, st));
-  HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, lcdev::launch_frontier_dump(d_ops, d_off, d_stop, n_keys, p, d_cfg, max_per_key, d_n,
+                                         d_retry, &d.d_status->n_overflow, st));
+  if ((e = read_status(c, d, st))) return e;
   // keys whose search outgrew the LDS regions: again over HBM tables (the
   // first HBM tier's 16k configurations per set), one wavefront per key
   if (const int32_t n_retry = d.h_status->n_overflow) {
     const int waves = std::min<int>(n_retry, 256);
-    if (!(e = ensure(c, reinterpret_cast<char **>(&d.d_ws), &d.ws_cap,
-                     lcdev::hbm_tier_ws_bytes(waves, kHbmCap[0]))))
-      HIP_TRY(c, lcdev::launch_frontier_dump_hbm(d_ops, d.d_off, d_stop, d.d_jit2, n_retry, p, d.d_ws,
-                                                 waves, kHbmCap[0], d_cfg, max_per_key, d.d_jit,
-                                                 &d.d_status->hbm_next, st));
-    else
-      return e;
+    if ((e = ensure(c, d.d_ws, lcdev::hbm_tier_ws_bytes(waves, kHbmCap[0])))) return e;
+    HIP_TRY(c, lcdev::launch_frontier_dump_hbm(d_ops, d_off, d_stop, d_retry, n_retry, p, d.d_ws.p, waves,
+                                               kHbmCap[0], d_cfg, max_per_key, d_n,
+                                               &d.d_status->hbm_next, st));
   }
   HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
-  HIP_TRY(c, hipMemcpyAsync(n_out, d.d_jit, sizeof(int32_t) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(n_out, d_n, sizeof(int32_t) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
   // one copy of every key's slots (C5's 94 keys x 10: 0.5 MB) rather than one
   // per key; slots past a key's count keep the device's scratch
   HIP_TRY(c, hipMemcpyAsync(out, d_cfg, cfg_bytes, hipMemcpyDeviceToHost, st));
@@ -2374,13 +2443,7 @@ int lc_pack32(const lc_op *ops, const int64_t *key_off, int64_t n_keys, lc_op32 
   };
   const int64_t n_rec = key_off[n_keys] - key_off[0];
   const int nth = (int)std::min<int64_t>(16, std::max<int64_t>(1, std::min<int64_t>(n_keys, n_rec >> 18)));
-  if (nth <= 1) {
-    pack(0, n_keys);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; t++) th.emplace_back(pack, n_keys * t / nth, n_keys * (t + 1) / nth);
-    for (auto &x : th) x.join();
-  }
+  for_key_ranges(n_keys, nth, pack);
   return 0;
 }
 
@@ -2424,13 +2487,7 @@ int lc_pack16(const lc_op *ops, const int64_t *key_off, int64_t n_keys, lc_op16 
   };
   const int64_t n_rec = key_off[n_keys] - key_off[0];
   const int nth = (int)std::min<int64_t>(16, std::max<int64_t>(1, std::min<int64_t>(n_keys, n_rec >> 18)));
-  if (nth <= 1) {
-    pack(0, n_keys);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; t++) th.emplace_back(pack, n_keys * t / nth, n_keys * (t + 1) / nth);
-    for (auto &x : th) x.join();
-  }
+  for_key_ranges(n_keys, nth, pack);
   return range.load() ? 0 : -ERANGE;
 }
 
