@@ -102,6 +102,16 @@ typedef struct lc_opts {
                                    several keys at once, each over a whole GPU.  A failed
                                    re-search leaves that key :unknown (text in lc_last_error);
                                    the call still returns 0 */
+#define LC_FLAG_COUNTED_CLASSES 32 /* every entry point: a key the tiers leave :unknown with
+                                   LC_REASON_WINDOW_OVERFLOW is searched again, on its device,
+                                   by the counted tier, which keeps one count per class of
+                                   equal crashed writes/CAS instead of a window slot per
+                                   crashed op (lc_counted_plan, lincheck_counted.h: the layout
+                                   and its limit); its result replaces the tiers'.  A key that does
+                                   not fit the layout stays as it was.  With LC_FLAG_WHOLE_GPU
+                                   the counted tier runs first and the frontier exchange
+                                   takes what is still :unknown.  Callers detect the feature
+                                   by looking up lc_counted_plan (LC_ABI_VERSION stays 5) */
 
 /* Verdicts: Knossos :valid? true / false / :unknown. */
 #define LC_VALID    1
@@ -112,7 +122,9 @@ typedef struct lc_opts {
 #define LC_REASON_NONE            0
 #define LC_REASON_NONLINEARIZABLE 1 /* frontier emptied at fail_op's return */
 #define LC_REASON_CONFIG_BUDGET   2 /* max_configs_per_key exceeded  -> :unknown */
-#define LC_REASON_WINDOW_OVERFLOW 3 /* > LC_MAX_WINDOW ops open at once -> :unknown */
+#define LC_REASON_WINDOW_OVERFLOW 3 /* > LC_MAX_WINDOW ops open at once -> :unknown (with
+                                       LC_FLAG_COUNTED_CLASSES: the key does not fit the counted
+                                       layout, or more than its `slots` other ops are open) */
 #define LC_REASON_MALFORMED       4 /* record out of range / unsorted -> this key :unknown (the call
                                        still returns 0, as jepsen.independent loses only that key) */
 #define LC_REASON_UNKNOWN_F       5 /* f not in {read,write,cas}: model throws (register.clj:63) -> :unknown */
@@ -120,7 +132,10 @@ typedef struct lc_opts {
 #define LC_REASON_TIME_BUDGET     7 /* lc_opts.time_budget_ms exceeded by the frontier search -> :unknown */
 
 /* Largest number of simultaneously open (called, not yet returned, or
- * crashed-but-unlinearized) operations one key may have. */
+ * crashed-but-unlinearized) operations one key may have.  With
+ * LC_FLAG_COUNTED_CLASSES crashed writes/CAS are counted per class and hold
+ * no slot; the limit is then lc_counted_layout.slots open ops of the other
+ * kinds. */
 #define LC_MAX_WINDOW 64
 
 /*
@@ -506,5 +521,8 @@ const char *lc_build_id(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* LC_FLAG_COUNTED_CLASSES: lc_counted_plan, lc_last_counted_stats */
+#include "lincheck_counted.h"
 
 #endif /* LINCHECK_H */

@@ -41,6 +41,8 @@ LC_FLAG_NO_FAST_PATH = 2
 LC_FLAG_NO_GAP_TIER = 4
 LC_FLAG_WHOLE_GPU = 8
 LC_FLAG_NO_TIMING = 16
+LC_FLAG_COUNTED_CLASSES = 32
+LC_COUNTED_MAX_CLASSES = 16
 LC_WITNESS_NONE, LC_WITNESS_FULL, LC_WITNESS_PREFIX = 0, 1, 2
 LC_CERT_NONE, LC_CERT_DUP, LC_CERT_UNREACH, LC_CERT_CLAIMS, LC_CERT_PAIR, LC_CERT_ORDER, \
     LC_CERT_HALL, LC_CERT_PROOF = range(8)
@@ -93,6 +95,19 @@ class LcCallProfile(ctypes.Structure):
 class LcTotals(ctypes.Structure):
     _fields_ = [("calls", ctypes.c_int64), ("timed_calls", ctypes.c_int64),
                 ("fast_kernel_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double)]
+
+
+class LcCountedLayout(ctypes.Structure):
+    _fields_ = [("n_classes", ctypes.c_int32), ("field_bits", ctypes.c_int32),
+                ("slots", ctypes.c_int32), ("fits", ctypes.c_int32)] + \
+               [(f, ctypes.c_int64 * LC_COUNTED_MAX_CLASSES)
+                for f in ("f", "value", "expected", "version", "members")] + \
+               [(f, ctypes.c_int32 * LC_COUNTED_MAX_CLASSES) for f in ("shift", "width")]
+
+
+class LcCountedStats(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_int64), ("n_decided", ctypes.c_int64),
+                ("n_unfit", ctypes.c_int64), ("kernel_ms", ctypes.c_double)]
 
 
 class LcAux(ctypes.Structure):
@@ -197,6 +212,10 @@ def lib():
         L.lc_default_opts.restype = None
         L.lc_plan_partition.argtypes = [p, p, i64, i32, p]
         L.lc_plan_partition.restype = ctypes.c_int
+        L.lc_counted_plan.argtypes = [p, i64, ctypes.POINTER(LcCountedLayout)]
+        L.lc_counted_plan.restype = ctypes.c_int
+        L.lc_last_counted_stats.argtypes = [vp, ctypes.POINTER(LcCountedStats)]
+        L.lc_last_counted_stats.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -321,6 +340,15 @@ class Context:
         s = into if into is not None else LcStats()
         lib().lc_last_stats(self._h, ctypes.byref(s))
         return s
+
+    def counted_stats(self):
+        """lc_last_counted_stats: the counted tier's share of the last call
+        (LC_FLAG_COUNTED_CLASSES), summed over its devices."""
+        s = LcCountedStats()
+        rc = lib().lc_last_counted_stats(self._h, ctypes.byref(s))
+        if rc != 0:
+            raise LcError(rc, "lc_last_counted_stats")
+        return {f: getattr(s, f) for f, _ in LcCountedStats._fields_}
 
     def device_stats(self):
         """lc_last_device_stats for every device of the last lc_check: one
@@ -540,6 +568,24 @@ def plan_partition(key_off, n_parts, ops=None):
     if rc != 0:
         raise LcError(rc, "lc_plan_partition")
     return bounds
+
+
+def counted_plan(records):
+    """lc_counted_plan: the class table the counted tier
+    (LC_FLAG_COUNTED_CLASSES) uses for one key's records, as a dict —
+    n_classes, field_bits, slots, fits, and `classes`: per class (the first
+    LC_COUNTED_MAX_CLASSES) f, value, expected, version, members, shift,
+    width.  Host-only."""
+    ops = as_ops(records)
+    lay = LcCountedLayout()
+    rc = lib().lc_counted_plan(_ptr(ops), len(ops), ctypes.byref(lay))
+    if rc != 0:
+        raise LcError(rc, "lc_counted_plan")
+    per = ("f", "value", "expected", "version", "members", "shift", "width")
+    n = min(int(lay.n_classes), LC_COUNTED_MAX_CLASSES)
+    return {"n_classes": int(lay.n_classes), "field_bits": int(lay.field_bits),
+            "slots": int(lay.slots), "fits": int(lay.fits),
+            "classes": [{f: int(getattr(lay, f)[c]) for f in per} for c in range(n)]}
 
 
 def key_cost(ops, key_off):

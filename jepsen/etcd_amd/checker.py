@@ -102,7 +102,8 @@ class RegisterChecker:
     result is then one key's map (no :results)."""
 
     def __init__(self, model=None, device_mask=0, max_configs_per_key=0, independent=True,
-                 timeline_dir=None, time_budget_ms=0, whole_gpu=True, frontier_max_keys=1000):
+                 timeline_dir=None, time_budget_ms=0, whole_gpu=True, frontier_max_keys=1000,
+                 counted_classes=True):
         self.model = model or VersionedRegister(0, None)
         # cap on the frontier re-searches one check() runs for diagnostics of
         # witnessed invalid keys (each is one key's search up to its failing
@@ -118,6 +119,14 @@ class RegisterChecker:
         # knossos keeps searching until it runs out of memory or time, so the
         # drop-in does too by default (time_budget_ms bounds it)
         self.whole_gpu = whole_gpu
+        # a key the tiers leave :unknown because more than 64 ops were open at
+        # once is searched again with its crashed writes/CAS counted per class
+        # (LC_FLAG_COUNTED_CLASSES), one wavefront per key inside the same
+        # call, before the whole-GPU re-search: the same results, 21x
+        # sooner for keys that hold one configuration (mutex histories) and
+        # 1.1x for frontiers of a few thousand; keys with frontiers of tens
+        # of thousands are quicker with counted_classes=False
+        self.counted_classes = counted_classes
         self._ctx = None
         self._fx = None
 
@@ -146,7 +155,8 @@ class RegisterChecker:
         # starts free (id MUTEX_FREE)
         init = H.MUTEX_FREE if m.name == "mutex" else (0 if m.value is not None else H.LC_NIL)
         o = abi.default_opts(self.max_configs_per_key, m.version, init,
-                             flags=abi.LC_FLAG_WHOLE_GPU if self.whole_gpu else 0,
+                             flags=(abi.LC_FLAG_WHOLE_GPU if self.whole_gpu else 0) |
+                             (abi.LC_FLAG_COUNTED_CLASSES if self.counted_classes else 0),
                              time_budget_ms=self.time_budget_ms)
         # the drop-in's call (ABI 5): 16-byte records when every value id
         # fits 15 bits, else 24-byte ones — what crosses PCIe (the JVM shim

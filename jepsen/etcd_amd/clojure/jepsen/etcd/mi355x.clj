@@ -54,6 +54,7 @@
 
 (def ^:const LC_NIL -1)
 (def ^:const LC_FLAG_WHOLE_GPU 8)  ; include/lincheck.h
+(def ^:const LC_FLAG_COUNTED_CLASSES 32)
 (def ^:const LC_INF Long/MAX_VALUE)
 (def ^:const op-bytes 48)      ; lc_op (the frontier searches)
 (def ^:const op32-bytes 24)    ; lc_op32 (lc_check32, ABI 4)
@@ -567,15 +568,18 @@
   models this library packs: opts :model one of :versioned-register,
   :cas-register, :register, :mutex.  The lock workload's checker
   (lock.clj:243-244) becomes (linearizable {:model :mutex})."
-  [{:keys [model max-configs-per-key time-budget-ms whole-gpu?]
-    :or {model :versioned-register max-configs-per-key 0 time-budget-ms 0 whole-gpu? true}}]
+  [{:keys [model max-configs-per-key time-budget-ms whole-gpu? counted-classes?]
+    :or {model :versioned-register max-configs-per-key 0 time-budget-ms 0 whole-gpu? true
+         counted-classes? true}}]
   (reify checker/Checker
     (check [_ test history _opts]
       (let [ops (filterv client-op? history)]
         (if (empty? ops)
           {:valid? true :analyzer :mi355x}
           (get (check-keys model max-configs-per-key time-budget-ms
-                           (if whole-gpu? LC_FLAG_WHOLE_GPU 0) {nil ops}) nil))))))
+                           (bit-or (if whole-gpu? LC_FLAG_WHOLE_GPU 0)
+                                   (if counted-classes? LC_FLAG_COUNTED_CLASSES 0))
+                           {nil ops}) nil))))))
 
 (defn- render-linear!
   "What jepsen's checker/linearizable does with a failed analysis: knossos's
@@ -614,18 +618,25 @@
   :unknown, as knossos's aborts are), :whole-gpu? (default true: a key one
   workgroup's search leaves :unknown at the configuration budget is searched
   again over the whole GPU, LC_FLAG_WHOLE_GPU, include/lincheck_fx.h, as
-  knossos keeps searching until it runs out of memory or time)."
+  knossos keeps searching until it runs out of memory or time),
+  :counted-classes? (default true: a key left :unknown because more than 64
+  ops were open at once is searched again inside the call with its crashed
+  writes/CAS counted per class, LC_FLAG_COUNTED_CLASSES, before the whole-GPU
+  search; the same results, much sooner for many small-frontier keys, slower
+  for keys with frontiers of tens of thousands of configurations)."
   ([] (checker {}))
-  ([{:keys [max-configs-per-key model timeline? time-budget-ms whole-gpu?]
+  ([{:keys [max-configs-per-key model timeline? time-budget-ms whole-gpu? counted-classes?]
      :or {max-configs-per-key 0 model :versioned-register timeline? true time-budget-ms 0
-          whole-gpu? true}}]
+          whole-gpu? true counted-classes? true}}]
    (reify checker/Checker
      (check [_ test history opts]
        (let [subs (subhistories history)]
          (if (empty? subs)
            {:valid? true :results {} :failures []}
            (let [linear  (check-keys model max-configs-per-key time-budget-ms
-                                     (if whole-gpu? LC_FLAG_WHOLE_GPU 0) subs)
+                                     (bit-or (if whole-gpu? LC_FLAG_WHOLE_GPU 0)
+                                             (if counted-classes? LC_FLAG_COUNTED_CLASSES 0))
+                                     subs)
                  results (into (array-map)
                                (for [[k r] linear]
                                  [k (composed test opts k (get subs k) r timeline?)]))]

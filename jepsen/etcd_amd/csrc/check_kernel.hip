@@ -39,6 +39,7 @@
 
 #include "../../../include/lincheck_fx.h"
 #include "kernels.h"
+#include "counted.h"
 #include "records.h"
 #include "wave.h"
 #include "gapmatch.h"
@@ -3332,6 +3333,514 @@ __global__ __launch_bounds__(kWave) void hbm_tier_kernel(
   }
 }
 
+// ==================================================================
+// Counted tier (LC_FLAG_COUNTED_CLASSES)
+// ==================================================================
+//
+// check_key gives every open op a window slot, so a key with more than 64
+// outstanding crashed writes/CAS overflows it.  Crashed writes/CAS with equal
+// (f, value, expected, version) are interchangeable, and deadline order
+// linearizes them in call order, after every pending :ok member of the
+// class; so a configuration needs only HOW MANY members of each class it has
+// linearized.  This tier runs check_key's search (JIT with eager read
+// closure, deadline order, retirement; same results field for field) with
+// the configuration mask cut up by the layout rule of counted.h:
+//   * class c owns a count field in the mask's top bits (absolute count, so
+//     equal configurations are equal words whatever has been retired) and
+//     lane 63 - c, whose Slot holds the class's precondition and effect, and
+//     whose pbit names the pending :ok members of the same tuple;
+//   * the low `slots` bits / lanes are check_key's window slots for every
+//     other open op;
+//   * the call of a crashed write/CAS takes no slot: it raises its class's
+//     `called`; class lane c is a candidate in (mask, state) iff it is legal
+//     in state, field(mask, c) < called and its pbit slots are linearized;
+//     its successor is mask + (1 << shift_c).
+// One wavefront per key over the one-wave HbmStore.
+struct Counted {
+  // lane 63 - c: class c's field, members and members called so far; else 0
+  int shift, width, members, called;
+  uint64_t clsmask;    // lanes that hold a class
+  uint64_t fieldmask;  // mask bits that hold counts
+  uint64_t slotmask;   // mask bits / lanes that are window slots
+};
+
+// Pre-pass over the key's records: the class table, by the layout rule.  Per
+// 64-record chunk, one ballot finds the crashed writes/CAS and one more per
+// distinct tuple among them its members.  Returns whether the key fits.
+__device__ bool counted_classes(const lc_op *__restrict__ kops, const int n, const int64_t base_idx,
+                                Slot &sl, Counted &cc, const int lane) {
+  cc = Counted{0, 0, 0, 0, 0ull, 0ull, ~0ull};
+  int ncls = 0;
+  for (int b = 0; b < n; b += kWave) {
+    const Rec r = decode(load_raw(kops, b + lane, n), base_idx);
+    uint64_t todo = __ballot((r.f == LC_F_WRITE || r.f == LC_F_CAS) && r.ret == kNever &&
+                             r.call != kNever);
+    while (todo) {
+      const int l = __builtin_ctzll(todo);
+      const int f = rl32(r.f, l), val = rl32(r.val, l), ex = rl32(r.exp, l), ver = rl32(r.ver, l);
+      const uint64_t same = todo & __ballot(r.f == f && r.val == val && r.exp == ex && r.ver == ver);
+      todo &= ~same;  // (l included)
+      const uint64_t hit =
+          __ballot(sl.f == f && sl.val == val && sl.exp == ex && sl.ver == ver) & cc.clsmask;
+      int cl;  // the class's lane
+      if (hit) {
+        cl = __builtin_ctzll(hit);
+      } else {
+        if (ncls == lccount::kCountedMaxClasses) return false;
+        cl = kWave - 1 - ncls++;
+        cc.clsmask |= 1ull << cl;
+        const int nv = rl32(r.nv, l), nvm = rl32(r.nvm, l), nl = rl32(r.nl, l), nlm = rl32(r.nlm, l);
+        if (lane == cl) {
+          sl.nv = nv;
+          sl.nvm = nvm;
+          sl.nl = nl;
+          sl.nlm = nlm;
+          sl.val = val;
+          sl.f = f;
+          sl.exp = ex;
+          sl.ver = ver;
+        }
+      }
+      if (lane == cl) cc.members += __popcll(same);
+    }
+  }
+  int bits = 0;
+  for (int c = 0; c < ncls; c++) {
+    const int cl = kWave - 1 - c;
+    const int w = lccount::counted_width(rl32(cc.members, cl));
+    bits += w;
+    if (lane == cl) {
+      cc.width = w;
+      cc.shift = 64 - bits;
+    }
+  }
+  const int slots = lccount::counted_slots(bits, ncls);
+  if (!lccount::counted_fits(ncls, slots)) return false;
+  cc.fieldmask = bits ? ~0ull << (64 - bits) : 0ull;
+  cc.slotmask = slots == 64 ? ~0ull : (1ull << slots) - 1;
+  return true;
+}
+
+// This lane's class has members called and not yet linearized in mask m
+// (false on lanes without a class: width 0, called 0).
+__device__ __forceinline__ bool counted_room(const Counted &cc, uint64_t m) {
+  return (int)((m >> cc.shift) & ((1ull << cc.width) - 1)) < cc.called;
+}
+
+// mutation_candidates with class lanes (wave-uniform configuration).
+__device__ __forceinline__ uint64_t counted_candidates(const Slot &sl, const Masks &mk,
+                                                       const Counted &cc, uint64_t cm, int ver,
+                                                       int val) {
+  uint64_t cand = legal_ballot(sl, ver, val) &
+                  ((mk.occ & ~mk.rdm & ~cm) | (cc.clsmask & __ballot(counted_room(cc, cm))));
+  cand &= __ballot((sl.pbit & ~cm) == 0);  // deadline order within a class
+  return cand;
+}
+
+// legal_by_state for a window in which no lane constrains the version (the
+// version-less models this tier is for): one ballot per distinct VALUE among
+// the lanes' states.  A batch's configurations differ in their versions (one
+// per mutation linearized), so by (version, value) nearly every lane has a
+// state of its own; by value they share a handful.  by_value false: as
+// legal_by_state.
+__device__ __forceinline__ uint64_t counted_legal(const int4 &spre, int ver, int val, bool act,
+                                                  bool by_value) {
+  if (!by_value) return legal_by_state(spre, ver, val, act);
+  uint64_t legal = 0;
+  bool todo = act;
+  for (uint64_t pend = __ballot(todo); pend; pend = __ballot(todo)) {
+    const int sval = rl32(val, __builtin_ctzll(pend));
+    const uint64_t m = __ballot(pre_ok(spre.x, 0, spre.z, spre.w, 0, sval));
+    if (todo && val == sval) {
+      legal = m;
+      todo = false;
+    }
+  }
+  return legal;
+}
+
+// general_return_par_try with class lanes: one attempt with this return's
+// table size; -3 when a role outgrows it.
+__device__ __forceinline__ int counted_return_try(HbmStore &st, const Slot &sl, const Masks &mk,
+                                                  const Counted &cc, int s, int rF, int rR, int rW,
+                                                  int nF, const KParams &p, KeyOut &o, int lane,
+                                                  bool value_only) {
+  const uint64_t bs = 1ull << s;
+  st.begin_return();
+  const int lim = st.lim(1);
+  int nR = 0, nW = 0;
+  for (int j0 = 0; j0 < nF; j0 += kWave) {  // split F into R and W
+    const int j = j0 + lane;
+    const bool v = j < nF;
+    Cfg c{0, 0};
+    if (v) c = st.get(rF, j);
+    const bool has = v && (c.mask & bs);
+    const bool lacks = v && !(c.mask & bs);
+    const uint64_t mh = __ballot(has), ml = __ballot(lacks);
+    if (has) st.add_unique_lane(ROLE_R, rR, nR + lanes_below(mh), Cfg{c.mask & ~bs, c.sv});
+    if (lacks) st.add_unique_lane(ROLE_W, rW, nW + lanes_below(ml), c);
+    nR += __popcll(mh);
+    nW += __popcll(ml);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  const uint64_t muts = mk.occ & ~mk.rdm, reads = mk.occ & mk.rdm;
+  const int4 spre = make_int4(sl.nv, sl.nvm, sl.nl, sl.nlm);  // lane t: slot / class lane t
+  const uint64_t ordered = __ballot(sl.pbit != 0);
+  // no pending slot and no class constrains the version: legality by value
+  const bool by_value = value_only && (__ballot(sl.nvm != 0) & (mk.occ | cc.clsmask)) == 0;
+  for (int head = 0; head < nW;) {
+    const int j = head + lane;
+    const bool act = j < nW;
+    const int taken = min(kWave, nW - head);
+    const Cfg c = st.get(rW, act ? j : head);
+    const int cver = sv_ver(c.sv), cval = sv_val(c.sv);
+    const uint64_t legal = counted_legal(spre, cver, cval, act, by_value);
+    uint64_t cand = legal & muts & ~c.mask;
+    for (uint64_t m = muts & ordered; m; m &= m - 1) {
+      const int t = __builtin_ctzll(m);
+      if (rl64(sl.pbit, t) & ~c.mask) cand &= ~(1ull << t);
+    }
+    for (uint64_t m = cc.clsmask; m; m &= m - 1) {  // class lanes: room, and no pending :ok member
+      const int t = __builtin_ctzll(m);
+      const int sh = rl32(cc.shift, t), wd = rl32(cc.width, t), called = rl32(cc.called, t);
+      const uint64_t pb = rl64(sl.pbit, t);
+      if ((int)((c.mask >> sh) & ((1ull << wd) - 1)) < called && (pb & ~c.mask) == 0)
+        cand |= legal & (1ull << t);
+    }
+    for (;;) {
+      const bool has = cand != 0;
+      const uint64_t hb = __ballot(has);
+      if (!hb) break;
+      const int t = has ? __builtin_ctzll(cand) : 0;
+      cand &= cand - 1;
+      const int nver = cver + 1, nval = __shfl(sl.val, t);
+      const int sh = __shfl(cc.shift, t);
+      uint64_t nm = ((cc.clsmask >> t) & 1) ? c.mask + (1ull << sh) : c.mask | (1ull << t);
+      nm |= counted_legal(spre, nver, nval, has, by_value) & reads;  // eager read closure
+      const bool toR = (nm & bs) != 0;
+      const Cfg nc{toR ? nm & ~bs : nm, pack_sv(nver, nval)};
+      o.explored += __popcll(hb);
+      const int ins = st.insert_lanes(toR ? ROLE_R : ROLE_W, nc, has);
+      const bool insR = ins && toR, insW = ins && !toR;
+      const uint64_t bR = __ballot(insR), bW = __ballot(insW);
+      if (nR + __popcll(bR) > lim || nW + __popcll(bW) > lim) return lim < st.cap ? -3 : -1;
+      if (insR) st.reg(rR)[nR + lanes_below(bR)] = nc;
+      if (insW) st.reg(rW)[nW + lanes_below(bW)] = nc;
+      nR += __popcll(bR);
+      nW += __popcll(bW);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      if (o.explored > p.budget) return -2;
+    }
+    head += taken;
+  }
+  st.hint = max(st.hint, max(nR, nW));
+  return nR;
+}
+
+__device__ __forceinline__ int counted_return(HbmStore &st, const Slot &sl, const Masks &mk,
+                                              const Counted &cc, int s, int rF, int rR, int rW,
+                                              int nF, const KParams &p, KeyOut &o, int lane,
+                                              bool value_only) {
+  st.tmask = st.pick_tmask(nF, 1024u);
+  const int64_t explored0 = o.explored;
+  for (;;) {  // (each redo has a 4x table, up to the workspace's: at most 11)
+    const int r = counted_return_try(st, sl, mk, cc, s, rF, rR, rW, nF, p, o, lane, value_only);
+    if (r != -3) return r;
+    o.explored = explored0;
+    st.tmask = st.grow_tmask();
+  }
+}
+
+// check_key with counted classes.  o.reason LC_REASON_WINDOW_OVERFLOW: the
+// key does not fit the layout, or more than its slots are open at once.
+__device__ void counted_key(const lc_op *__restrict__ kops, const int n, const KParams &p,
+                            HbmStore &st, KeyOut &o, const int lane, const bool value_only) {
+  o.verdict = LC_VALID;
+  o.reason = LC_REASON_NONE;
+  o.fail_op = -1;
+  o.fail_end = -1;
+  o.explored = 1;
+  o.max_frontier = 1;
+  if (n <= 0) return;
+
+  Slot sl{0, 0, 0, 0, -1, 0, -1, -1, -1, kNever, 0ull};
+  Masks mk{0, 0, 0};
+  Counted cc;
+  const int64_t base_idx = kops[0].call;
+  if (!counted_classes(kops, n, base_idx, sl, cc, lane)) {
+    o.verdict = LC_UNKNOWN;
+    o.reason = LC_REASON_WINDOW_OVERFLOW;
+    return;
+  }
+
+  // Frontier: ONE configuration in SGPRs — its state fsv and its counts fcnt
+  // (no slot is linearized in it: retirement) — or nF configurations in rF.
+  bool single = true;
+  uint64_t fsv = pack_sv(p.init_ver, p.init_val), fcnt = 0;
+  int rF = 0, rR = 1, rW = 2, nF = 1;
+
+  const uint64_t t0 = p.time_ticks ? wall_clock64() : 0;
+  uint32_t last_call = kNever;
+  Rec cur = decode(load_raw(kops, lane, n), base_idx);
+  check_order(cur, last_call, lane);
+  ChunkMasks cmk = chunk_masks(cur, fsv);
+  uint64_t crashmut = __ballot(cur.f != LC_F_READ && cur.ret == kNever);  // counted at their call
+  Raw nxt = load_raw(kops, kWave + lane, n);
+  int base = 0, i = 0;
+
+  for (;;) {
+    const uint32_t ncall = (i < n) ? (uint32_t)rl32((int)cur.call, i - base) : kNever;
+    const uint64_t due = __ballot(sl.ret < ncall);
+    if (due == 0) {
+      if (i >= n) break;
+      // ------------------------------------------------------- call of op i
+      const int li = i - base;
+      const uint64_t bit = 1ull << li;
+      if (cmk.special & bit) {
+        o.verdict = LC_UNKNOWN;
+        o.reason = rl32(cur.bad, li) ? LC_REASON_MALFORMED : LC_REASON_UNKNOWN_F;
+        return;
+      }
+      const bool done = (cmk.isread & bit) &&
+                        ((cmk.skip & bit) || (single && (cmk.legal_now & bit)));
+      if (crashmut & bit) {  // one more member of its class may be linearized
+        const int f = rl32(cur.f, li), val = rl32(cur.val, li);
+        const int ex = rl32(cur.exp, li), ver = rl32(cur.ver, li);
+        if (sl.f == f && sl.val == val && sl.exp == ex && sl.ver == ver && ((cc.clsmask >> lane) & 1))
+          cc.called++;
+      } else if (!done) {
+        if ((mk.occ & cc.slotmask) == cc.slotmask) {
+          o.verdict = LC_UNKNOWN;
+          o.reason = LC_REASON_WINDOW_OVERFLOW;
+          return;
+        }
+        const int s = __builtin_ctzll(~mk.occ);
+        const uint64_t bs = 1ull << s;
+        const int f = rl32(cur.f, li), val = rl32(cur.val, li);
+        const int ex = rl32(cur.exp, li), ver = rl32(cur.ver, li);
+        const int nv = rl32(cur.nv, li), nvm = rl32(cur.nvm, li);
+        const int nl = rl32(cur.nl, li), nlm = rl32(cur.nlm, li);
+        const uint32_t ret = (uint32_t)rl32((int)cur.ret, li);
+        uint64_t pbit = 0;
+        if (f != LC_F_READ) {
+          // deadline order among the :ok members in slots, as check_key; the
+          // tuple's class lane (crashed: the latest deadline) waits for s
+          const uint64_t eq = __ballot(sl.f == f && sl.val == val && sl.exp == ex && sl.ver == ver);
+          const uint64_t cls = eq & mk.occ & ~mk.rdm;
+          pbit = cls & __ballot(sl.ret <= ret);
+          if ((((cls & ~pbit) | (eq & cc.clsmask)) >> lane) & 1) sl.pbit |= bs;
+        }
+        if (lane == s) {
+          sl.nv = nv;
+          sl.nvm = nvm;
+          sl.nl = nl;
+          sl.nlm = nlm;
+          sl.val = val;
+          sl.f = f;
+          sl.exp = ex;
+          sl.ver = ver;
+          sl.idx = i;
+          sl.ret = ret;
+          sl.pbit = pbit;
+        }
+        mk.occ |= bs;
+        if (f == LC_F_READ) {
+          mk.rdm |= bs;
+          if (!single) {  // eager read closure at the call, per configuration
+            for (int j = lane; j < nF; j += kWave) {
+              const Cfg c = st.get(rF, j);
+              if (pre_ok(nv, nvm, nl, nlm, sv_ver(c.sv), sv_val(c.sv)))
+                st.set_mask_lane(rF, j, c.mask | bs);
+            }
+          }
+        }
+      }
+      i++;
+      if (i - base == kWave) {
+        base += kWave;
+        cur = decode(nxt, base_idx);
+        check_order(cur, last_call, lane);
+        cmk = chunk_masks(cur, fsv);
+        crashmut = __ballot(cur.f != LC_F_READ && cur.ret == kNever);
+        nxt = load_raw(kops, base + kWave + lane, n);
+      }
+      continue;
+    }
+
+    // ----------------------------------------------------- return of x
+    int s;
+    if ((due & (due - 1)) == 0) {
+      s = __builtin_ctzll(due);
+    } else {
+      const bool mine = (due >> lane) & 1;
+      const uint32_t m = wave_min_u32(mine ? sl.ret : kNever);
+      s = __builtin_ctzll(__ballot(mine && sl.ret == m));
+    }
+    const uint64_t bs = 1ull << s;
+    const int x_idx = rl32(sl.idx, s);
+    const uint32_t nret = (uint32_t)rl32((int)sl.ret, s);
+    bool empty = false;
+    if (single) {
+      // chain walk in SGPRs, the counts carried in cm's fields
+      const int64_t explored0 = o.explored;
+      uint64_t cm = fcnt, csv = fsv;
+      bool branch = false;
+      for (;;) {
+        const int cver = sv_ver(csv), cval = sv_val(csv);
+        const uint64_t cand = counted_candidates(sl, mk, cc, cm, cver, cval);
+        if (cand == 0) {
+          empty = true;
+          break;
+        }
+        if (cand & (cand - 1)) {
+          branch = true;
+          break;
+        }
+        const int t = __builtin_ctzll(cand);
+        const int nver = cver + 1;
+        const int nval = rl32(sl.val, t);
+        uint64_t nm = ((cc.clsmask >> t) & 1) ? cm + (1ull << rl32(cc.shift, t)) : cm | (1ull << t);
+        nm |= read_closure(sl, mk, nm, nver, nval);
+        o.explored++;
+        if (o.explored > p.budget) {
+          o.verdict = LC_UNKNOWN;
+          o.reason = LC_REASON_CONFIG_BUDGET;
+          return;
+        }
+        cm = nm;
+        csv = pack_sv(nver, nval);
+        if (nm & bs) break;
+      }
+      if (branch) {
+        o.explored = explored0;
+        single = false;
+        rF = 0;
+        rR = 1;
+        rW = 2;
+        nF = 1;
+        if (lane == 0) st.reg(rF)[0] = Cfg{fcnt, fsv};
+      } else if (!empty) {
+        fsv = csv;
+        fcnt = cm & cc.fieldmask;
+        retire(sl, mk, cm & ~cc.fieldmask, lane);  // x included
+        cmk.legal_now = cmk.isread &
+                        __ballot(pre_ok(cur.nv, cur.nvm, cur.nl, cur.nlm, sv_ver(fsv), sv_val(fsv)));
+      }
+    }
+    if (!single) {
+      if (p.time_ticks && wall_clock64() - t0 > p.time_ticks) {
+        o.verdict = LC_UNKNOWN;
+        o.reason = LC_REASON_TIME_BUDGET;
+        return;
+      }
+      const int r = counted_return(st, sl, mk, cc, s, rF, rR, rW, nF, p, o, lane, value_only);
+      if (r < 0) {
+        o.verdict = LC_UNKNOWN;
+        o.reason = r == -1 ? LC_REASON_FRONTIER_LDS : LC_REASON_CONFIG_BUDGET;
+        return;
+      }
+      const int t = rF;
+      rF = rR;
+      rR = t;
+      nF = r;
+      if (nF > o.max_frontier) o.max_frontier = nF;
+      empty = nF == 0;
+      if (!empty) {
+        retire(sl, mk, bs, lane);  // x returned
+        // slots linearized in every configuration (occ holds no field bit:
+        // counted members never need retiring)
+        uint64_t acc = ~0ull;
+        for (int j = lane; j < nF; j += kWave) acc &= st.get(rF, j).mask;
+        const uint64_t rb = mk.occ & wave_and_u64(acc);
+        if (rb) {
+          retire(sl, mk, rb, lane);
+          for (int j = lane; j < nF; j += kWave)
+            st.set_mask_lane(rF, j, st.get(rF, j).mask & ~rb);
+        }
+        if (nF == 1) {  // back to the register-resident frontier (its slot bits now empty)
+          const Cfg c = st.get(rF, 0);
+          fsv = rfl64(c.sv);
+          fcnt = rfl64(c.mask) & cc.fieldmask;
+          single = true;
+          cmk.legal_now = cmk.isread &
+                          __ballot(pre_ok(cur.nv, cur.nvm, cur.nl, cur.nlm, sv_ver(fsv), sv_val(fsv)));
+        }
+      }
+    }
+    if (empty) {
+      o.verdict = LC_INVALID;
+      o.reason = LC_REASON_NONLINEARIZABLE;
+      o.fail_op = x_idx;
+      o.fail_end = base_idx + (int64_t)nret;
+      return;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kWave) void counted_tier_kernel(
+    const lc_op *__restrict__ ops, const int64_t *__restrict__ key_off,
+    const int32_t *__restrict__ keys, const int32_t n_list, const KParams p,
+    lc_key_result *__restrict__ out, char *__restrict__ ws, const int64_t cap,
+    int32_t *__restrict__ ovf_out, int32_t *__restrict__ n_ovf_out, KStatus *__restrict__ status,
+    const int last_tier, const int value_only) {
+  const int lane = threadIdx.x;
+  char *w = ws + (size_t)blockIdx.x * hbm_wave_bytes(cap);
+  HbmStore st;
+  st.base = reinterpret_cast<Cfg *>(w);
+  st.tabs = st.base + 3 * cap;
+  st.tags = reinterpret_cast<uint32_t *>(st.tabs + 4 * cap);
+  st.cap = (int)cap;
+  st.tmask = st.tmask_full = (uint32_t)(2 * cap - 1);
+  hbm_zero_tags(st.tags, cap);
+  st.epoch = 0;  // epochs start at 1
+  const int64_t key_base = key_off[0];
+  for (;;) {  // list entries claimed one at a time (hbm_next: zero at launch)
+    int li = 0;
+    if (lane == 0) li = atomicAdd(&status->hbm_next, 1);
+    li = uni(li);
+    if (li >= n_list) break;
+    const int64_t key = keys[li];
+    const int64_t beg = key_off[key], end = key_off[key + 1];
+    KeyOut o;
+    st.hint = 0;
+    counted_key(ops + (beg - key_base), (int)(end - beg), p, st, o, lane, value_only != 0);
+    if (o.reason == LC_REASON_FRONTIER_LDS && last_tier)
+      o.reason = LC_REASON_CONFIG_BUDGET;  // largest sets full: give up
+    if (lane == 0) {
+      if (o.reason == LC_REASON_WINDOW_OVERFLOW) {  // the tiers' result stays
+        atomicAdd(&status->n_counted_unfit, 1);
+      } else if (o.reason == LC_REASON_FRONTIER_LDS) {
+        ovf_out[atomicAdd(n_ovf_out, 1)] = (int32_t)key;  // next, larger capacity
+      } else {
+        if (o.reason == LC_REASON_MALFORMED) atomicAdd(&status->malformed, 1);
+        if (o.verdict != LC_UNKNOWN) atomicAdd(&status->n_counted_decided, 1);
+        write_result(&out[key], o);
+      }
+    }
+  }
+}
+
+// The keys the tiers left :unknown with LC_REASON_WINDOW_OVERFLOW, listed
+// for the counted tier: one list reservation per wavefront.
+__global__ __launch_bounds__(256) void counted_compact_kernel(
+    const lc_key_result *__restrict__ out, const int64_t n_keys, int32_t *__restrict__ keys,
+    int32_t *__restrict__ n) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // (whole wavefronts iterate together: k0 is the wave's first key)
+  for (int64_t k0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; k0 < n_keys; k0 += stride) {
+    const int64_t k = k0 + lane;
+    const bool take = k < n_keys && out[k].verdict == LC_UNKNOWN &&
+                      out[k].reason == LC_REASON_WINDOW_OVERFLOW;
+    const uint64_t b = __ballot(take);
+    if (!b) continue;
+    int pos = 0;
+    if (lane == 0) pos = atomicAdd(n, __popcll(b));
+    pos = uni(pos);
+    if (take) keys[pos + lanes_below(b)] = (int32_t)k;
+  }
+}
+
 // The same over HBM tables (the one-wave HBM tier's store, workspace of
 // hbm_wave_bytes(cap) per wave), for the listed keys, claimed one at a time.
 __global__ __launch_bounds__(kWave) void frontier_dump_hbm_kernel(
@@ -3893,6 +4402,26 @@ hipError_t launch_hbm_tier(const lc_op *d_ops, const int64_t *d_key_off,
                      stream, d_ops, d_key_off, d_keys, n_list, p,
                      d_out, static_cast<char *>(d_ws), cap, d_ovf_out, d_n_ovf_out, d_malformed,
                      d_next, last_tier);
+  return hipGetLastError();
+}
+
+hipError_t launch_counted_compact(const lc_key_result *d_out, int64_t n_keys, int32_t *d_keys,
+                                  int32_t *d_n, hipStream_t stream) {
+  if (n_keys <= 0) return hipSuccess;
+  const int64_t blocks = std::min<int64_t>((n_keys + 255) / 256, 1024);
+  hipLaunchKernelGGL(counted_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_out,
+                     n_keys, d_keys, d_n);
+  return hipGetLastError();
+}
+
+hipError_t launch_counted_tier(const lc_op *d_ops, const int64_t *d_key_off, const int32_t *d_keys,
+                               int32_t n_list, const KParams &p, lc_key_result *d_out, void *d_ws,
+                               int n_waves, int64_t cap, int32_t *d_ovf_out, int32_t *d_n_ovf_out,
+                               KStatus *d_status, int last_tier, int value_only, hipStream_t stream) {
+  if (n_list <= 0) return hipSuccess;
+  hipLaunchKernelGGL(counted_tier_kernel, dim3((unsigned)n_waves), dim3(kWave), 0, stream, d_ops,
+                     d_key_off, d_keys, n_list, p, d_out, static_cast<char *>(d_ws), cap, d_ovf_out,
+                     d_n_ovf_out, d_status, last_tier, value_only);
   return hipGetLastError();
 }
 

@@ -43,6 +43,9 @@ struct KStatus {
   // queued behind one another and held up the workgroups' stores and loads
   // (fused pass 0.166 -> 0.121 ms without it)
   int32_t n_light_sh[32 * 32];
+  // counted tier (LC_FLAG_COUNTED_CLASSES): keys listed for it, keys it
+  // decided, keys it left untouched at LC_REASON_WINDOW_OVERFLOW
+  int32_t n_counted, n_counted_decided, n_counted_unfit;
 };
 constexpr int kLightShards = 32, kLightStride = 32;
 __host__ __device__ inline int32_t *light_shard(KStatus *s, int64_t key) {
@@ -248,6 +251,27 @@ hipError_t launch_hbm_tier(const lc_op *d_ops, const int64_t *d_key_off,
                            void *d_ws, int n_waves, int64_t cap,
                            int32_t *d_ovf_out, int32_t *d_n_ovf_out, int32_t *d_malformed,
                            int32_t *d_next, int last_tier, hipStream_t stream);
+
+// Counted tier (LC_FLAG_COUNTED_CLASSES; check_kernel.hip, "Counted tier"):
+// launch_counted_compact lists the keys of d_out left :unknown with
+// LC_REASON_WINDOW_OVERFLOW in d_keys (count *d_n, zero at launch);
+// launch_counted_tier searches them again, one wavefront per key over the
+// one-wave HBM store (workspace hbm_tier_ws_bytes(n_waves, cap), keys claimed
+// from *d_next, zero at launch), with the crashed writes/CAS counted per
+// class by the layout rule of counted.h.  A key that does not fit the layout,
+// or overflows its slots, keeps its result (status->n_counted_unfit); one
+// whose sets outgrow cap goes to d_ovf_out (*d_n_ovf_out) for the next
+// capacity, or becomes LC_REASON_CONFIG_BUDGET on the last; a decided one
+// counts in status->n_counted_decided.  value_only: returns at which nothing
+// constrains the version test legality per distinct value of the batch's
+// states instead of per distinct (version, value); 0 is the A/B and test knob
+// LC_COUNTED_BY_VALUE=0 (same results).
+hipError_t launch_counted_compact(const lc_key_result *d_out, int64_t n_keys, int32_t *d_keys,
+                                  int32_t *d_n, hipStream_t stream);
+hipError_t launch_counted_tier(const lc_op *d_ops, const int64_t *d_key_off, const int32_t *d_keys,
+                               int32_t n_list, const KParams &p, lc_key_result *d_out, void *d_ws,
+                               int n_waves, int64_t cap, int32_t *d_ovf_out, int32_t *d_n_ovf_out,
+                               KStatus *d_status, int last_tier, int value_only, hipStream_t stream);
 
 // Gap tier (gap_tier.hip): version-pinned keys with crashed writes/CAS are
 // decided by matching gaps to optional ops; keys it cannot decide are

@@ -31,6 +31,7 @@
 #include "../../../include/lincheck.h"
 #include "../../../include/lincheck_fx.h"
 #include "kernels.h"
+#include "counted.h"
 
 #ifndef LC_BUILD_ID
 #define LC_BUILD_ID "unknown"
@@ -193,6 +194,7 @@ struct Dev {
   double kernel_ms = 0, fast_ms = 0, gap_ms = 0, jit_ms = 0, hbm_ms = 0;
   int64_t n_gap = 0, n_jit = 0, n_hbm = 0;
   int malformed = 0;
+  lc_counted_stats counted{};               // this device's share of lc_last_counted_stats
   lc_device_stats last{};                   // this device's share of the last lc_check
   double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
   // this device's share of lc_last_totals: written only by the device's own
@@ -676,6 +678,7 @@ int begin_call(Run &r) {
   d.kernel_ms = d.hbm_ms = d.fast_ms = d.jit_ms = d.gap_ms = 0;
   d.n_hbm = d.n_jit = d.n_gap = 0;
   d.malformed = 0;
+  d.counted = lc_counted_stats{};
   if (r.n_keys <= 0) return 0;
   if (r.n_keys > INT32_MAX) {
     set_err(c, "lc_check: more than 2^31-1 keys in one call");
@@ -1144,6 +1147,48 @@ int hbm_tiers(Run &r) {
   return 0;
 }
 
+// LC_FLAG_COUNTED_CLASSES: the keys the tiers left :unknown with
+// LC_REASON_WINDOW_OVERFLOW (listed on the device from d_out) are searched
+// again with their crashed writes/CAS counted per class (kernels.h
+// launch_counted_tier), over the HBM tiers' ladder of set capacities.  Runs
+// after every tier's event time has been read (e1 / e2 are free again); the
+// counters it uses are zero on entry as all of d_status is.
+int counted_tier(Run &r) {
+  if (!(r.flags & LC_FLAG_COUNTED_CLASSES)) return 0;
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  int32_t *list = d.d_ovf.p, *next = d.d_ovf2.p;
+  HIP_TRY(c, hipEventRecord(d.e1, st));
+  HIP_TRY(c, lcdev::launch_counted_compact(r.d_out, r.n_keys, list, &d.d_status->n_counted, st));
+  if (int e = read_status(c, d, st)) return e;
+  int32_t n_list = d.h_status->n_counted;
+  d.counted.n_keys = n_list;
+  if (n_list <= 0) return 0;
+  const int by_value = !env_is_off("LC_COUNTED_BY_VALUE");
+  for (int tier = 0; tier < kHbmTiers && n_list > 0; tier++) {
+    const int waves = std::min<int>(kHbmWaves[tier], n_list);
+    if (int rc = ensure(c, d.d_ws, lcdev::hbm_tier_ws_bytes(waves, kHbmCap[tier]))) return rc;
+    HIP_TRY(c, hipMemsetAsync(&d.d_status->n_overflow2, 0, sizeof(int32_t), st));
+    HIP_TRY(c, hipMemsetAsync(&d.d_status->hbm_next, 0, sizeof(int32_t), st));
+    HIP_TRY(c, lcdev::launch_counted_tier(r.d_ops, r.d_off, list, n_list, r.p, r.d_out, d.d_ws.p, waves,
+                                          kHbmCap[tier], next, &d.d_status->n_overflow2, d.d_status,
+                                          tier == kHbmTiers - 1, by_value, st));
+    if (int e = read_status(c, d, st)) return e;
+    n_list = tier < kHbmTiers - 1 ? d.h_status->n_overflow2 : 0;
+    std::swap(list, next);
+  }
+  float ms = 0;
+  HIP_TRY(c, hipEventRecord(d.e2, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  HIP_TRY(c, hipEventElapsedTime(&ms, d.e1, d.e2));
+  d.counted.kernel_ms = ms;
+  d.counted.n_decided = d.h_status->n_counted_decided;
+  d.counted.n_unfit = d.h_status->n_counted_unfit;
+  d.malformed = d.h_status->malformed;
+  return 0;
+}
+
 // The later tiers ran: d_status back to zero (the invariant between calls),
 // the call's totals.
 int end_call(Run &r) {
@@ -1156,7 +1201,7 @@ int end_call(Run &r) {
     d.tot.timed_calls++;
     d.tot.fast_kernel_ms += d.fast_ms;
   }
-  d.tot.kernel_ms += d.kernel_ms + d.hbm_ms;
+  d.tot.kernel_ms += d.kernel_ms + d.hbm_ms + d.counted.kernel_ms;
   return 0;
 }
 
@@ -1177,7 +1222,7 @@ int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int6
   if (int e = first_pass(r, &handed)) return e;
   if (handed)
     if (int e = handoff(r)) return e;
-  if (r.n_jit == 0 && r.n_direct == 0) {  // every key decided
+  if (r.n_jit == 0 && r.n_direct == 0) {  // every key decided (none left for the counted tier)
     d.kernel_ms = d.fast_ms + d.gap_ms;
     if (!d.timing_pending && r.timing) {
       d.tot.timed_calls++;
@@ -1193,6 +1238,7 @@ int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int6
   if (int e = gap_tier(r)) return e;
   if (int e = search_tier(r)) return e;
   if (int e = hbm_tiers(r)) return e;
+  if (int e = counted_tier(r)) return e;
   return end_call(r);
 }
 
@@ -1581,6 +1627,7 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
   };
   c->stats = lc_stats{};
   c->prof = lc_call_profile{};
+  for (Dev &d : c->devs) d.counted = lc_counted_stats{};  // (a device without keys runs nothing)
   if (n_keys < 0 || (n_keys > 0 && (!ops || !key_off || !out))) {
     set_err(c, "lc_check: null buffer or negative n_keys");
     return -EINVAL;
@@ -1961,6 +2008,7 @@ int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const 
                  void *stream, const lc_aux *aux) {
   const auto t0 = std::chrono::steady_clock::now();
   c->stats = lc_stats{};
+  for (Dev &d : c->devs) d.counted = lc_counted_stats{};
   if (n_keys < 0 || (n_keys > 0 && (!ops || !d_key_off || !d_out))) {
     set_err(c, std::string(who) + ": null buffer or negative n_keys");
     return -EINVAL;
@@ -2167,6 +2215,59 @@ int lc_quiesce(lc_ctx *c) {
     (void)hipSetDevice(d.id);
     if (int e = res_stop(c, d)) return e;
   }
+  return 0;
+}
+
+int lc_last_counted_stats(lc_ctx *c, lc_counted_stats *out) {
+  if (!c || !out) return -EINVAL;
+  lc_counted_stats s{};
+  for (const Dev &d : c->devs) {
+    s.n_keys += d.counted.n_keys;
+    s.n_decided += d.counted.n_decided;
+    s.n_unfit += d.counted.n_unfit;
+    s.kernel_ms += d.counted.kernel_ms;
+  }
+  *out = s;
+  return 0;
+}
+
+int lc_counted_plan(const lc_op *ops, int64_t n, lc_counted_layout *out) {
+  if (!out || n < 0 || (n > 0 && !ops)) return -EINVAL;
+  *out = lc_counted_layout{};
+  struct Cls {
+    int64_t f, value, expected, version, members;
+  };
+  std::vector<Cls> cls;  // in order of first call (records are sorted by call)
+  for (int64_t i = 0; i < n; i++) {
+    const lc_op &o = ops[i];
+    if ((o.f != LC_F_WRITE && o.f != LC_F_CAS) || o.ret != LC_INF) continue;
+    const int64_t ver = lccount::counted_version(o.version);
+    auto it = std::find_if(cls.begin(), cls.end(), [&](const Cls &k) {
+      return k.f == o.f && k.value == o.value && k.expected == o.expected && k.version == ver;
+    });
+    if (it == cls.end()) cls.push_back(Cls{o.f, o.value, o.expected, ver, 1});
+    else it->members++;
+  }
+  int64_t bits = 0;
+  for (size_t k = 0; k < cls.size(); k++) {
+    const int w = lccount::counted_width(cls[k].members);
+    bits += w;
+    if (k < (size_t)LC_COUNTED_MAX_CLASSES) {
+      out->f[k] = cls[k].f;
+      out->value[k] = cls[k].value;
+      out->expected[k] = cls[k].expected;
+      out->version[k] = cls[k].version;
+      out->members[k] = cls[k].members;
+      out->width[k] = w;
+      out->shift[k] = (int32_t)(64 - bits);
+    }
+  }
+  const int64_t ncls = (int64_t)cls.size();
+  out->n_classes = (int32_t)std::min<int64_t>(ncls, INT32_MAX);
+  out->field_bits = (int32_t)std::min<int64_t>(bits, INT32_MAX);
+  // (beyond int: far from fitting either way)
+  out->slots = (int32_t)std::max<int64_t>(std::min(64 - bits, 64 - ncls), INT32_MIN);
+  out->fits = lccount::counted_fits(out->n_classes, out->slots);
   return 0;
 }
 
