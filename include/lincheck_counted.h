@@ -66,6 +66,55 @@ typedef struct lc_counted_stats {
 
 int lc_last_counted_stats(lc_ctx *ctx, lc_counted_stats *out);
 
+/*
+ * knossos's :configs from the counted search, batched: lc_check_frontiers
+ * (lincheck_fx.h) for keys with more ops open than its window holds, and with
+ * pending lists of any length.  For every key, one wavefront runs the counted
+ * tier's search up to the :ok return of record stop_op[k] (key-relative; an
+ * invalid key's fail_op) and returns the frontier that return expands, over
+ * the tier's ladder of set capacities.  Additive to ABI 5 (callers look the
+ * symbol up); LC_FLAG_COUNTED_CLASSES is not needed, this call always counts.
+ * Like lc_check_frontiers it runs on the context's first GPU over the
+ * context's scratch buffers, and takes max_configs_per_key / time_budget_ms /
+ * init_* from opts.
+ *
+ *   out[k * max_per_key + j]   configuration j of key k, j < n_out[k]
+ *   pending[pending_at ...]    its n_pending pending ops: key-relative record
+ *                              indices, sorted; pending_at = max_per_key *
+ *                              (key_off[k] - key_off[0]) + j * n_k with n_k the
+ *                              key's records (a pending set is never larger)
+ *   n_out[k]                   configurations copied, at most max_per_key
+ *   n_total[k]                 the frontier's size
+ *
+ * n_out[k] = n_total[k] = 0 when the stop op's return is a no-op (the op had
+ * been linearized in every configuration), and -1 when the search could not
+ * get there: the key does not fit lc_counted_plan's rule or has more than
+ * `slots` other ops open at once, has a malformed record, the configuration
+ * or time budget ran out, the key failed before that return, stop_op[k] is
+ * not an :ok op of the key, or the frontier outgrew the top capacity.  Slots
+ * of `out` and `pending` past a key's count are left as they were.
+ *
+ * A configuration's pending ops are the open ops not linearized in it; of a
+ * class's crashed members, which the search linearizes in call order, the
+ * ones from the first not linearized on.  Ops linearized in every
+ * configuration are retired and pending in none.
+ *
+ * Returns 0, -EINVAL (null ctx or buffer, n_keys < 0, max_per_key < 1,
+ * key_off not monotone, pending_cap < max_per_key * (key_off[n_keys] -
+ * key_off[0]); message in lc_last_error), -ENOMEM or -EIO.
+ */
+typedef struct lc_counted_config {
+  int64_t version, value; /* value: the caller's id; LC_NIL for nil */
+  int64_t n_pending;      /* the whole pending set, no cap */
+  int64_t pending_at;     /* index into `pending` of its sorted record indices */
+} lc_counted_config;
+
+int lc_check_frontiers_counted(lc_ctx *ctx, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
+                               const int64_t *stop_op, const lc_opts *opts,
+                               lc_counted_config *out, int32_t max_per_key,
+                               int32_t *n_out, int64_t *n_total,
+                               int64_t *pending, int64_t pending_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,7 +147,11 @@ int lc_fx_check(lc_fx *fx, const lc_op *ops, int64_t n, const lc_opts *opts,
  * the model state and the ops (record indices of the key) that have been
  * called but are not linearized in it.  Ops linearized in every
  * configuration are retired and never pending; reads that can never
- * constrain (crashed, [nil nil]) take no part in the search. */
+ * constrain (crashed, [nil nil]) take no part in the search.  At most 64
+ * pending ops are listed: lc_fx_frontier fills the first 64 of a larger
+ * pending set (a key whose crashed writes/CAS it counts per class) and
+ * n_pending is then 64.  lc_check_frontiers_counted (lincheck_counted.h)
+ * returns such keys' configurations with their pending sets whole. */
 typedef struct lc_fx_config {
   int64_t version;
   int64_t value;        /* the caller's value id; LC_NIL for nil */
@@ -175,8 +179,9 @@ int lc_fx_frontier(lc_fx *fx, const lc_op *ops, int64_t n, const lc_opts *opts, 
  * stop_op's return is a no-op (the op was retired); -1 when the search could
  * not get there on the LDS tier (a frontier beyond 128 configurations, more
  * than LC_MAX_WINDOW open ops, the budget, an earlier failure, a stop_op that
- * is not an :ok op): lc_fx_frontier decides those one by one.  Returns 0,
- * -EINVAL, -ENOMEM or -EIO. */
+ * is not an :ok op): lc_check_frontiers_counted (lincheck_counted.h) takes
+ * those with more than LC_MAX_WINDOW open ops, batched, and lc_fx_frontier
+ * decides the others one by one.  Returns 0, -EINVAL, -ENOMEM or -EIO. */
 int lc_check_frontiers(lc_ctx *ctx, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
                        const int64_t *stop_op, const lc_opts *opts, lc_fx_config *out,
                        int32_t max_per_key, int32_t *n_out);

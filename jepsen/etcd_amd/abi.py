@@ -110,6 +110,12 @@ class LcCountedStats(ctypes.Structure):
                 ("n_unfit", ctypes.c_int64), ("kernel_ms", ctypes.c_double)]
 
 
+# lc_counted_config (include/lincheck_counted.h)
+COUNTED_CONFIG_DTYPE = np.dtype([("version", "<i8"), ("value", "<i8"), ("n_pending", "<i8"),
+                                 ("pending_at", "<i8")])
+assert COUNTED_CONFIG_DTYPE.itemsize == 32
+
+
 class LcAux(ctypes.Structure):
     _fields_ = [("witness", ctypes.c_void_p), ("witness_kind", ctypes.c_void_p),
                 ("certificate", ctypes.c_void_p), ("certificate_set", ctypes.c_void_p)]
@@ -216,6 +222,10 @@ def lib():
         L.lc_counted_plan.restype = ctypes.c_int
         L.lc_last_counted_stats.argtypes = [vp, ctypes.POINTER(LcCountedStats)]
         L.lc_last_counted_stats.restype = ctypes.c_int
+        if hasattr(L, "lc_check_frontiers_counted"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            L.lc_check_frontiers_counted.argtypes = [vp, p, p, i64, p, ctypes.POINTER(LcOpts), p, i32,
+                                                     p, p, p, i64]
+            L.lc_check_frontiers_counted.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -459,6 +469,49 @@ class Context:
             out.append([(int(c.version), int(c.value), tuple(int(c.pending[j]) for j in range(c.n_pending)))
                         for c in buf[k * max_per_key:k * max_per_key + n]])
         return out
+
+    def check_frontiers_counted(self, ops, key_off, stop_ops, max_per_key=10, opts=None):
+        """lc_check_frontiers_counted (include/lincheck_counted.h): as
+        check_frontiers, from the counted search — keys with more than 64 ops
+        open, every pending list whole.  Returns (configs, totals):
+        configs[k] is None where the search could not get there, else up to
+        max_per_key (version, value id, pending record indices) tuples;
+        totals[k] (int64) is the frontier's size, -1 with None."""
+        ops = as_ops(ops)
+        key_off = np.ascontiguousarray(key_off, dtype=np.int64)
+        n_keys = len(key_off) - 1
+        stop = np.ascontiguousarray(stop_ops, dtype=np.int64)
+        if len(stop) != n_keys:
+            raise ValueError(f"stop_ops has {len(stop)} entries for {n_keys} keys")
+        if n_keys <= 0:
+            return [], np.zeros(0, dtype=np.int64)
+        cap = int(max_per_key) * int(key_off[-1] - key_off[0])
+        cfg = np.zeros(n_keys * max(int(max_per_key), 0), dtype=COUNTED_CONFIG_DTYPE)
+        pending = np.empty(max(cap, 1), dtype=np.int64)
+        n_out = np.zeros(n_keys, dtype=np.int32)
+        totals = np.zeros(n_keys, dtype=np.int64)
+        o = opts if opts is not None else default_opts()
+        rc = lib().lc_check_frontiers_counted(self._h, _ptr(ops), _ptr(key_off), n_keys, _ptr(stop),
+                                              ctypes.byref(o), _ptr(cfg), max_per_key, _ptr(n_out),
+                                              _ptr(totals), _ptr(pending), cap)
+        if rc != 0:
+            raise LcError(rc, self.last_error())
+        out = []
+        for k in range(n_keys):
+            n = int(n_out[k])
+            if n <= 0:
+                out.append(None if n < 0 else [])
+                continue
+            c = cfg[k * max_per_key:k * max_per_key + n]
+            # one slice of `pending` per configuration, one tolist() per key
+            at, npend = c["pending_at"], c["n_pending"]
+            idx = np.repeat(at - np.concatenate(([0], np.cumsum(npend)[:-1])), npend) + \
+                np.arange(int(npend.sum()))
+            flat = pending[idx].tolist()
+            ends = np.cumsum(npend).tolist()
+            out.append([(v, x, tuple(flat[e - m:e])) for v, x, m, e in
+                        zip(c["version"].tolist(), c["value"].tolist(), npend.tolist(), ends)])
+        return out, totals
 
     def quiesce(self):
         """lc_quiesce (ABI 5): stop the resident version-order grid now (it

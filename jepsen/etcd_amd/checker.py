@@ -24,8 +24,10 @@ timeline.html on the host (timeline.py), as jepsen's timeline/html would.
 An invalid key's map also carries knossos's diagnostics (diagnostics.py):
 "previous-ok", "configs" and "final-paths" — from the search's own frontier
 just before the failing return (up to 10 configurations: one batched device
-search over every invalid key, lc_check_frontiers, and lc_fx_frontier for a
-key whose frontier outgrows it), and "last-op" from the witness of the prefix
+search over every invalid key, lc_check_frontiers; one more over the counted
+search, lc_check_frontiers_counted, for the keys with more than 64 ops open,
+whose pending lists it returns whole; and lc_fx_frontier for a key neither
+takes), and "last-op" from the witness of the prefix
 before the failing return (lc_aux) for keys the version-order and gap tiers
 decided.
 
@@ -171,7 +173,10 @@ class RegisterChecker:
             ops32, key_base = abi.pack32(ops, key_off)
             _, res, wit, kind, cert, cset = self._context().check32(
                 ops32, key_off, key_base, o, witness=True, certificate=True)
-        cfgs_of = self._configs(ops, key_off, res, o)
+        witnessed_keys = kind == abi.LC_WITNESS_PREFIX if m.name == "versioned-register" \
+            else [False] * len(keys)
+        cfg_errors = {}
+        cfgs_of = self._configs(ops, key_off, res, o, witnessed_keys, cfg_errors)
         results = {}
         n_fallback = 0  # one-key frontier re-searches run for diagnostics in this call
         for i, k in enumerate(keys):
@@ -202,16 +207,18 @@ class RegisterChecker:
                 witnessed = m.name == "versioned-register" and kind[i] == abi.LC_WITNESS_PREFIX
                 # knossos's :configs are its search's frontier just before the
                 # failing return: every invalid key's came from one batched
-                # device search (lc_check_frontiers, _configs); a key that
-                # search could not take (its frontier outgrew the LDS tier) is
-                # re-searched alone by the frontier exchange (lc_fx_frontier)
+                # device search (lc_check_frontiers, _configs), or for a key
+                # with more than 64 ops open from one more over the counted
+                # search (lc_check_frontiers_counted); a key neither could
+                # take is re-searched alone by the frontier exchange
+                # (lc_fx_frontier, which lists at most 64 pending ops)
                 # — any key the search decided, and witnessed keys with at
                 # most FRONTIER_MAX_CRASHED crashed ops — at most
                 # frontier_max_keys such re-searches per call (the Clojure
                 # shim counts the same way); beyond that, or if the re-search
                 # fails, the witness's one configuration (with
                 # "configs-error" saying why)
-                cfgs, err = cfgs_of.get(i), None
+                cfgs, err = cfgs_of.get(i), cfg_errors.get(i)
                 if cfgs is None and n_fallback < self.frontier_max_keys and (
                         not witnessed or
                         int((recs[:, 5] == abi.LC_INF).sum()) <= FRONTIER_MAX_CRASHED):
@@ -256,25 +263,46 @@ class RegisterChecker:
                 "results": results,
                 "failures": [k for k, r in results.items() if r["valid?"] is False]}
 
-    def _configs(self, ops, key_off, res, opts):
+    def _configs(self, ops, key_off, res, opts, witnessed=None, errors=None):
         """knossos's :configs of every invalid key in one device call
-        (lc_check_frontiers): {key index: [(version, value id, pending)]},
-        the keys the device search could not take left out."""
+        (lc_check_frontiers), and of the keys it left out — more than 64 ops
+        open — in one more over the counted search
+        (lc_check_frontiers_counted): {key index: [(version, value id,
+        pending)]}, the keys neither search could take left out.  The second
+        call takes the keys the one-key fallback would take (`witnessed`:
+        bool per key; a witnessed key only with at most FRONTIER_MAX_CRASHED
+        crashed ops); if it fails, they get its error in `errors` and fall
+        back as before."""
         import numpy as np
         inv = np.nonzero(res["verdict"] == abi.LC_INVALID)[0]
         if self.frontier_max_keys <= 0 or len(inv) == 0:
             return {}
-        parts = [ops[key_off[i]:key_off[i + 1]] for i in inv]
-        sub_off = np.zeros(len(inv) + 1, dtype=np.int64)
-        sub_off[1:] = np.cumsum([len(x) for x in parts])
+
+        def sub(idx):
+            parts = [ops[key_off[i]:key_off[i + 1]] for i in idx]
+            sub_off = np.zeros(len(idx) + 1, dtype=np.int64)
+            sub_off[1:] = np.cumsum([len(x) for x in parts])
+            return np.concatenate(parts), sub_off
+
         try:
-            got = self._context().check_frontiers(np.concatenate(parts), sub_off,
-                                                  res["fail_op"][inv], D.MAX_ENTRIES, opts)
+            got = self._context().check_frontiers(*sub(inv), res["fail_op"][inv], D.MAX_ENTRIES, opts)
         except Exception:  # noqa: BLE001 — diagnostics only; the verdicts stand
             # (as mi355x.clj batched-configs): every key falls back to the
             # one-key re-search or its witness
             return {}
-        return {int(i): c for i, c in zip(inv, got) if c is not None}
+        out = {int(i): c for i, c in zip(inv, got) if c is not None}
+        rest = [int(i) for i in inv if int(i) not in out and (
+            witnessed is None or not witnessed[i] or
+            int((ops[key_off[i]:key_off[i + 1], 5] == abi.LC_INF).sum()) <= FRONTIER_MAX_CRASHED)]
+        if rest:
+            try:
+                got, _ = self._context().check_frontiers_counted(
+                    *sub(rest), res["fail_op"][rest], D.MAX_ENTRIES, opts)
+                out.update({i: c for i, c in zip(rest, got) if c is not None})
+            except abi.LcError as e:
+                if errors is not None:
+                    errors.update({i: repr(e) for i in rest})
+        return out
 
     def _composed(self, k, linear, subs):
         """checker/compose's per-key map (register.clj:109-112)."""

@@ -34,8 +34,11 @@
   :previous-ok, :configs and :final-paths — up to 10 configurations of the
   JIT search's frontier just before the failing return, for every invalid
   key from one batched device search (lc_check_frontiers,
-  include/lincheck_fx.h) and, for a key whose frontier outgrows it, from the
-  frontier exchange alone (lc_fx_frontier); for keys the version-order and
+  include/lincheck_fx.h), for the keys with more than 64 ops open from one
+  more over the counted search (lc_check_frontiers_counted,
+  include/lincheck_counted.h: pending lists whole) and, for a key neither
+  takes, from the frontier exchange alone (lc_fx_frontier, at most 64 pending
+  ops listed); for keys the version-order and
   gap tiers decided, also the :last-op of the prefix witness (lc_aux); the
   witness's one configuration stands in where no frontier could be had.  :final-paths step the reference's own model
   (jepsen.etcd.register/->VersionedRegister, register.clj:55-96) through
@@ -363,6 +366,7 @@
          :final-paths (final-paths done fail-op [[state last-i pending]])}))))
 
 (def ^:const fx-config-bytes 536)  ; lc_fx_config: version, value, n_pending, pending[64]
+(def ^:const counted-config-bytes 32)  ; lc_counted_config: version, value, n_pending, pending_at
 
 (defonce ^:private fx-engine
   (delay
@@ -398,13 +402,59 @@
          [(.getLong buf b) (.getLong buf (+ b 8))
           (vec (for [j (range (.getLong buf (+ b 16)))] (.getLong buf (+ b 24 (* 8 j)))))])))
 
+(defn- read-counted-configs
+  "n lc_counted_config structs (include/lincheck_counted.h) from buf at byte
+  offset b0, their pending record indices from `pending`."
+  [^Memory buf b0 n ^Memory pending]
+  (vec (for [i (range n)
+             :let [b  (+ b0 (* i counted-config-bytes))
+                   at (.getLong buf (+ b 24))]]
+         [(.getLong buf b) (.getLong buf (+ b 8))
+          (vec (for [j (range (.getLong buf (+ b 16)))] (.getLong pending (* 8 (+ at j)))))])))
+
+(defn- counted-configs
+  "The keys lc_check_frontiers left out (more than 64 ops open) in one call
+  over the counted search (lc_check_frontiers_counted, additive to ABI 5:
+  looked up, and skipped when the library has no such symbol): {key-index
+  configurations} for the keys it answers, pending lists whole."
+  [model done inv o]
+  (if-let [f (try (fun "lc_check_frontiers_counted") (catch UnsatisfiedLinkError _ nil))]
+    (let [kis        (mapv first inv)
+          [ops offs] (pack48 model done kis)
+          nk         (count kis)
+          nrec       (aget ^longs offs nk)
+          off        (doto (Memory. (* 8 (inc nk))) (.write 0 offs 0 (alength offs)))
+          stops      (long-array (map second inv))
+          stop       (doto (Memory. (* 8 nk)) (.write 0 stops 0 (alength stops)))
+          buf        (Memory. (* nk 10 counted-config-bytes))
+          cnt        (Memory. (* 4 nk))
+          tot        (Memory. (* 8 nk))
+          pcap       (* 10 nrec)
+          pending    (Memory. (* 8 (max 1 pcap)))
+          rc         (try
+                       (locking ctx
+                         (.invokeInt ^Function f
+                                     (object-array [@ctx ops off (long nk) stop o buf (int 10) cnt tot
+                                                    pending (long pcap)])))
+                       ;; diagnostics only: the verdict stands whatever happens here
+                       (catch Exception e e))]
+      (if (and (number? rc) (zero? rc))
+        (into {} (for [j (range nk)
+                       :let [c (.getInt cnt (* 4 j))]
+                       :when (>= c 0)]
+                   [(nth kis j) (read-counted-configs buf (* j 10 counted-config-bytes) c pending)]))
+        {}))
+    {}))
+
 (defn- batched-configs
   "knossos's :configs of every invalid key in one device call
-  (lc_check_frontiers, include/lincheck_fx.h): {:configs {key-index
-  configurations}, :ops ^Memory, :off long[], :at {key-index j}} — the keys the
-  device search could not take (a frontier beyond its tiers) are left out of
-  :configs; :ops / :off / :at hold their 48-byte records for lc_fx_frontier."
-  [model done inv o]
+  (lc_check_frontiers, include/lincheck_fx.h), and of the keys it left out
+  for which (counted? key-index) holds in one more over the counted search
+  (counted-configs): {:configs {key-index configurations}, :ops ^Memory, :off
+  long[], :at {key-index j}} — the keys neither search could take are left
+  out of :configs; :ops / :off / :at hold their 48-byte records for
+  lc_fx_frontier."
+  [model done inv o counted?]
   (let [kis         (mapv first inv)
         [ops offs]  (pack48 model done kis)
         nk          (count kis)
@@ -419,14 +469,16 @@
                                     (object-array [@ctx ops off (long nk) stop o buf (int 10) cnt])))
                       ;; diagnostics only: the verdict stands whatever happens here
                       (catch Exception e e))
-        ok?         (and (number? rc) (zero? rc))]
+        ok?         (and (number? rc) (zero? rc))
+        slot        (if-not ok?
+                      {}
+                      (into {} (for [j (range nk)
+                                     :let [c (.getInt cnt (* 4 j))]
+                                     :when (>= c 0)]
+                                 [(nth kis j) (read-configs buf (* j 10 fx-config-bytes) c)])))
+        rest-inv    (when ok? (filterv (fn [[ki _]] (and (not (contains? slot ki)) (counted? ki))) inv))]
     {:ops ops :off offs :at (zipmap kis (range))
-     :configs (if-not ok?
-                {}
-                (into {} (for [j (range nk)
-                               :let [c (.getInt cnt (* 4 j))]
-                               :when (>= c 0)]
-                           [(nth kis j) (read-configs buf (* j 10 fx-config-bytes) c)])))}))
+     :configs (cond-> slot (seq rest-inv) (merge (counted-configs model done rest-inv o)))}))
 
 (defn- fx-frontier
   "One key's frontier search alone, up to its failing return
@@ -495,7 +547,13 @@
                          :let [b (* ki result-bytes)]
                          :when (zero? (.getInt out b))]
                      [ki (.getLong out (+ b 8))]))
-          bc  (when (seq inv) (batched-configs model done inv o))]
+          ;; the counted search's keys: the one-key fallback's gate
+          counted? (fn [ki]
+                     (or (not (and (= model :versioned-register)
+                                   (= 2 (.getInt kind (* 4 ki)))))  ; LC_WITNESS_PREFIX
+                         (<= (count (filter #(= LC_INF (:ret %)) (nth done ki)))
+                             frontier-max-crashed)))
+          bc  (when (seq inv) (batched-configs model done inv o counted?))]
       (into (array-map)
             (for [ki (range nk)]
               (let [b       (* ki result-bytes)

@@ -3551,10 +3551,54 @@ __device__ __forceinline__ int counted_return(HbmStore &st, const Slot &sl, cons
   }
 }
 
+// lc_check_frontiers_counted: counted_key<true> stops at the :ok return of
+// record `stop` (key-relative return stop_ret) as check_key<.., true> does
+// (DumpReq), and writes the frontier that return expands in compact form
+// (kernels.h CountedCfg / CountedKeyOut); n as DumpReq::n.  Wave-uniform.
+struct CountedDumpReq {
+  int stop;
+  uint32_t stop_ret;
+  CountedCfg *out;
+  CountedKeyOut *key;
+  int max;
+  int n;
+};
+static_assert(lccount::kCountedMaxClasses == 16, "CountedKeyOut holds 16 classes");
+
+// The frontier just before a return: the lone configuration (state fsv,
+// counts fcnt, every occupied slot pending), or region rF's first min(nF,
+// max) configurations, a lane each; and the key's tables at the stop.
+__device__ void counted_dump(const HbmStore &st, const Slot &sl, const Masks &mk, const Counted &cc,
+                             bool single, uint64_t fsv, uint64_t fcnt, int rF, int nF,
+                             CountedDumpReq &dr, int lane) {
+  const int total = single ? 1 : nF, m = min(total, dr.max);
+  for (int j = lane; j < m; j += kWave) {
+    Cfg c{fcnt, fsv};
+    if (!single) c = st.get(rF, j);
+    dr.out[j] = CountedCfg{sv_ver(c.sv), sv_val(c.sv), (c.mask & cc.fieldmask) | (mk.occ & ~c.mask)};
+  }
+  CountedKeyOut *k = dr.key;
+  k->slot_rec[lane] = ((mk.occ >> lane) & 1) ? sl.idx : -1;
+  if ((cc.clsmask >> lane) & 1) {
+    const int c = kWave - 1 - lane;
+    k->shift[c] = cc.shift;
+    k->width[c] = cc.width;
+    k->called[c] = cc.called;
+  }
+  if (lane == 0) {
+    k->n = m;
+    k->total = total;
+    k->n_classes = __popcll(cc.clsmask);
+  }
+  dr.n = m;
+}
+
 // check_key with counted classes.  o.reason LC_REASON_WINDOW_OVERFLOW: the
 // key does not fit the layout, or more than its slots are open at once.
+template <bool kDump = false>
 __device__ void counted_key(const lc_op *__restrict__ kops, const int n, const KParams &p,
-                            HbmStore &st, KeyOut &o, const int lane, const bool value_only) {
+                            HbmStore &st, KeyOut &o, const int lane, const bool value_only,
+                            CountedDumpReq *dreq = nullptr) {
   o.verdict = LC_VALID;
   o.reason = LC_REASON_NONE;
   o.fail_op = -1;
@@ -3592,6 +3636,12 @@ __device__ void counted_key(const lc_op *__restrict__ kops, const int n, const K
     const uint32_t ncall = (i < n) ? (uint32_t)rl32((int)cur.call, i - base) : kNever;
     const uint64_t due = __ballot(sl.ret < ncall);
     if (due == 0) {
+      if constexpr (kDump) {
+        if (ncall > dreq->stop_ret) {  // (i >= n included) its return came and went:
+          dreq->n = 0;                 // the op had been retired
+          return;
+        }
+      }
       if (i >= n) break;
       // ------------------------------------------------------- call of op i
       const int li = i - base;
@@ -3679,6 +3729,16 @@ __device__ void counted_key(const lc_op *__restrict__ kops, const int n, const K
     const uint64_t bs = 1ull << s;
     const int x_idx = rl32(sl.idx, s);
     const uint32_t nret = (uint32_t)rl32((int)sl.ret, s);
+    if constexpr (kDump) {
+      if (nret > dreq->stop_ret) {
+        dreq->n = 0;
+        return;
+      }
+      if (x_idx == dreq->stop) {
+        counted_dump(st, sl, mk, cc, single, fsv, fcnt, rF, nF, *dreq, lane);
+        return;
+      }
+    }
     bool empty = false;
     if (single) {
       // chain walk in SGPRs, the counts carried in cm's fields
@@ -3816,6 +3876,54 @@ __global__ __launch_bounds__(kWave) void counted_tier_kernel(
         if (o.verdict != LC_UNKNOWN) atomicAdd(&status->n_counted_decided, 1);
         write_result(&out[key], o);
       }
+    }
+  }
+}
+
+// launch_counted_frontier (kernels.h): counted_tier_kernel's wavefront per
+// listed key, the search stopped at the key's stop op and its frontier
+// written out instead of a result.
+__global__ __launch_bounds__(kWave) void counted_frontier_kernel(
+    const lc_op *__restrict__ ops, const int64_t *__restrict__ key_off,
+    const int64_t *__restrict__ stop_op, const int32_t *__restrict__ keys, const int32_t n_list,
+    const KParams p, char *__restrict__ ws, const int64_t cap, CountedCfg *__restrict__ out,
+    const int max, CountedKeyOut *__restrict__ keyout, int32_t *__restrict__ ovf_out,
+    int32_t *__restrict__ n_ovf_out, int32_t *__restrict__ next, const int last_tier,
+    const int value_only) {
+  const int lane = threadIdx.x;
+  char *w = ws + (size_t)blockIdx.x * hbm_wave_bytes(cap);
+  HbmStore st;
+  st.base = reinterpret_cast<Cfg *>(w);
+  st.tabs = st.base + 3 * cap;
+  st.tags = reinterpret_cast<uint32_t *>(st.tabs + 4 * cap);
+  st.cap = (int)cap;
+  st.tmask = st.tmask_full = (uint32_t)(2 * cap - 1);
+  hbm_zero_tags(st.tags, cap);
+  st.epoch = 0;
+  const int64_t key_base = key_off[0];
+  for (;;) {
+    int li = 0;
+    if (lane == 0) li = atomicAdd(next, 1);
+    li = uni(li);
+    if (li >= n_list) break;
+    const int64_t key = keys[li];
+    const int64_t beg = key_off[key], end = key_off[key + 1], stop = stop_op[key];
+    CountedDumpReq dr{(int)stop, kNever, out + key * max, keyout + key, max, -1};
+    bool retry = false;
+    if (end > beg && end - beg <= 0x7FFFFFFF && stop >= 0 && stop < end - beg) {
+      const lc_op *kops = ops + (beg - key_base);
+      const int64_t b0 = kops[0].call, r = kops[stop].ret;
+      if (r != kInf && r - b0 >= 0 && r - b0 < (int64_t)kNever) {  // (an :ok op's return)
+        dr.stop_ret = (uint32_t)(r - b0);
+        KeyOut o;
+        st.hint = 0;
+        counted_key<true>(kops, (int)(end - beg), p, st, o, lane, value_only != 0, &dr);
+        retry = dr.n < 0 && o.reason == LC_REASON_FRONTIER_LDS && !last_tier;
+      }
+    }
+    if (lane == 0) {
+      if (dr.n <= 0) keyout[key].n = keyout[key].total = dr.n;
+      if (retry) ovf_out[atomicAdd(n_ovf_out, 1)] = (int32_t)key;  // next, larger capacity
     }
   }
 }
@@ -4411,6 +4519,19 @@ hipError_t launch_counted_compact(const lc_key_result *d_out, int64_t n_keys, in
   const int64_t blocks = std::min<int64_t>((n_keys + 255) / 256, 1024);
   hipLaunchKernelGGL(counted_compact_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_out,
                      n_keys, d_keys, d_n);
+  return hipGetLastError();
+}
+
+hipError_t launch_counted_frontier(const lc_op *d_ops, const int64_t *d_key_off,
+                                   const int64_t *d_stop, const int32_t *d_keys, int32_t n_list,
+                                   const KParams &p, void *d_ws, int n_waves, int64_t cap,
+                                   CountedCfg *d_cfg, int max, CountedKeyOut *d_keyout,
+                                   int32_t *d_ovf_out, int32_t *d_n_ovf_out, int32_t *d_next,
+                                   int last_tier, int value_only, hipStream_t stream) {
+  if (n_list <= 0 || n_waves <= 0) return hipSuccess;
+  hipLaunchKernelGGL(counted_frontier_kernel, dim3((unsigned)n_waves), dim3(kWave), 0, stream, d_ops,
+                     d_key_off, d_stop, d_keys, n_list, p, static_cast<char *>(d_ws), cap, d_cfg, max,
+                     d_keyout, d_ovf_out, d_n_ovf_out, d_next, last_tier, value_only);
   return hipGetLastError();
 }
 

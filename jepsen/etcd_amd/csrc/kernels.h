@@ -273,6 +273,34 @@ hipError_t launch_counted_tier(const lc_op *d_ops, const int64_t *d_key_off, con
                                int n_waves, int64_t cap, int32_t *d_ovf_out, int32_t *d_n_ovf_out,
                                KStatus *d_status, int last_tier, int value_only, hipStream_t stream);
 
+// lc_check_frontiers_counted (include/lincheck_counted.h): the counted tier's
+// search of the listed keys up to the :ok return of record d_stop[key], the
+// frontier that return expands written in compact form — up to `max`
+// CountedCfg at d_cfg[key * max ...] and the tables that expand them in
+// d_keyout[key].  n: configurations written, 0 when the op's return was a
+// no-op, -1 when the search did not get there; total: the frontier's size.
+// A key whose sets outgrow cap is listed in d_ovf_out (*d_n_ovf_out, zero at
+// launch) for the next capacity unless last_tier.  Workspace, claiming and
+// value_only as launch_counted_tier.
+struct CountedCfg {
+  int32_t version, value;  // the state
+  // the mask's count fields (per class, the absolute number of members
+  // linearized) over its low bits: window slots pending in the configuration
+  uint64_t word;
+};
+struct CountedKeyOut {
+  int32_t n, total, n_classes, pad;
+  int32_t slot_rec[kWave];  // window slot -> key-relative record at the stop; -1: free
+  // class c (lccount order): its field in CountedCfg::word, members called by the stop
+  int32_t shift[16], width[16], called[16];
+};
+hipError_t launch_counted_frontier(const lc_op *d_ops, const int64_t *d_key_off,
+                                   const int64_t *d_stop, const int32_t *d_keys, int32_t n_list,
+                                   const KParams &p, void *d_ws, int n_waves, int64_t cap,
+                                   CountedCfg *d_cfg, int max, CountedKeyOut *d_keyout,
+                                   int32_t *d_ovf_out, int32_t *d_n_ovf_out, int32_t *d_next,
+                                   int last_tier, int value_only, hipStream_t stream);
+
 // Gap tier (gap_tier.hip): version-pinned keys with crashed writes/CAS are
 // decided by matching gaps to optional ops; keys it cannot decide are
 // appended to d_pass_keys (status->n_jit2).  A call runs two kinds of launch
