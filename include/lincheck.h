@@ -112,6 +112,17 @@ typedef struct lc_opts {
                                    the counted tier runs first and the frontier exchange
                                    takes what is still :unknown.  Callers detect the feature
                                    by looking up lc_counted_plan (LC_ABI_VERSION stays 5) */
+#define LC_FLAG_SEARCH_WITNESS 64 /* every entry point that takes lc_aux, with aux->witness and
+                                   aux->witness_kind both given: after the tiers (the counted tier
+                                   included), every key that is decided (LC_VALID / LC_INVALID) but
+                                   still has witness kind LC_WITNESS_NONE is searched once more,
+                                   depth first (Wing-Gong-Lowe with a cache of dead ends), for a
+                                   linearization: LC_WITNESS_ORDER_FULL / LC_WITNESS_ORDER_PREFIX
+                                   (lc_aux).  No lc_key_result changes, and a key the search gives
+                                   up on (lc_witness_stats) keeps kind NONE; keys re-decided by
+                                   LC_FLAG_WHOLE_GPU are not searched.  Without the flag every
+                                   output is what it was.  Callers detect the feature by
+                                   looking up lc_last_witness_stats (LC_ABI_VERSION stays 5) */
 
 /* Verdicts: Knossos :valid? true / false / :unknown. */
 #define LC_VALID    1
@@ -195,6 +206,20 @@ typedef struct lc_stats {
  *                order is checkable in O(n) by stepping the model
  *                (register.clj:60-96) and testing real-time order
  *                (tests/test_witness.py does exactly that, independently).
+ *                With LC_FLAG_SEARCH_WITNESS, a key a search tier decided gets
+ *                witness_kind ORDER_FULL (valid key): witness[r] = the rank
+ *                of record r in a total order of the ops linearized, 0 ..
+ *                L-1, each rank once; -1 when r is left out, which only a
+ *                record with ret == LC_INF may be — every :ok record is
+ *                ranked, reads included.  ORDER_PREFIX (invalid key): the
+ *                same for the history prefix at event cut = fail_prefix_end
+ *                - 1: records with call > cut are left out, records with
+ *                ret <= cut are ranked, the others may be either.  An order
+ *                is certified from the records alone: stepping the model
+ *                (register.clj:60-96) from (init_version, init_value) in rank
+ *                order is legal at every step, and for every ranked op b,
+ *                ret(b) is greater than the largest call among the ops
+ *                ranked before it (real time).
  *  witness_kind  one int32 per key, LC_WITNESS_*.
  */
 typedef struct lc_aux {
@@ -204,9 +229,13 @@ typedef struct lc_aux {
   int32_t *certificate_set;  /* ABI 3: one int32 per record, indexed like ops, or NULL */
 } lc_aux;
 
-#define LC_WITNESS_NONE   0  /* no witness: decided by a search tier, or :unknown */
+#define LC_WITNESS_NONE   0  /* no witness: decided by a search tier (and not searched
+                                again under LC_FLAG_SEARCH_WITNESS), or :unknown */
 #define LC_WITNESS_FULL   1  /* valid key: a linearization of the whole history */
 #define LC_WITNESS_PREFIX 2  /* invalid key: a linearization of the prefix just before the failing return */
+#define LC_WITNESS_ORDER_FULL   3  /* LC_FLAG_SEARCH_WITNESS, valid key: the rank of every linearized record */
+#define LC_WITNESS_ORDER_PREFIX 4  /* LC_FLAG_SEARCH_WITNESS, invalid key: the same for the prefix at
+                                      fail_prefix_end - 1 */
 
 /*
  * Infeasibility certificates (ABI 3).  The PREFIX witness shows that the
@@ -524,5 +553,7 @@ const char *lc_build_id(void);
 
 /* LC_FLAG_COUNTED_CLASSES: lc_counted_plan, lc_last_counted_stats */
 #include "lincheck_counted.h"
+/* LC_FLAG_SEARCH_WITNESS: lc_last_witness_stats */
+#include "lincheck_witness.h"
 
 #endif /* LINCHECK_H */

@@ -42,8 +42,10 @@ LC_FLAG_NO_GAP_TIER = 4
 LC_FLAG_WHOLE_GPU = 8
 LC_FLAG_NO_TIMING = 16
 LC_FLAG_COUNTED_CLASSES = 32
+LC_FLAG_SEARCH_WITNESS = 64
 LC_COUNTED_MAX_CLASSES = 16
 LC_WITNESS_NONE, LC_WITNESS_FULL, LC_WITNESS_PREFIX = 0, 1, 2
+LC_WITNESS_ORDER_FULL, LC_WITNESS_ORDER_PREFIX = 3, 4  # LC_FLAG_SEARCH_WITNESS (witness.py)
 LC_CERT_NONE, LC_CERT_DUP, LC_CERT_UNREACH, LC_CERT_CLAIMS, LC_CERT_PAIR, LC_CERT_ORDER, \
     LC_CERT_HALL, LC_CERT_PROOF = range(8)
 
@@ -108,6 +110,13 @@ class LcCountedLayout(ctypes.Structure):
 class LcCountedStats(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("n_decided", ctypes.c_int64),
                 ("n_unfit", ctypes.c_int64), ("kernel_ms", ctypes.c_double)]
+
+
+class LcWitnessStats(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_int64), ("n_found", ctypes.c_int64),
+                ("n_budget", ctypes.c_int64), ("n_window", ctypes.c_int64),
+                ("nodes", ctypes.c_int64), ("cache_hits", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
 
 
 # lc_counted_config (include/lincheck_counted.h)
@@ -222,6 +231,9 @@ def lib():
         L.lc_counted_plan.restype = ctypes.c_int
         L.lc_last_counted_stats.argtypes = [vp, ctypes.POINTER(LcCountedStats)]
         L.lc_last_counted_stats.restype = ctypes.c_int
+        if hasattr(L, "lc_last_witness_stats"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            L.lc_last_witness_stats.argtypes = [vp, ctypes.POINTER(LcWitnessStats)]
+            L.lc_last_witness_stats.restype = ctypes.c_int
         if hasattr(L, "lc_check_frontiers_counted"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
             L.lc_check_frontiers_counted.argtypes = [vp, p, p, i64, p, ctypes.POINTER(LcOpts), p, i32,
                                                      p, p, p, i64]
@@ -359,6 +371,15 @@ class Context:
         if rc != 0:
             raise LcError(rc, "lc_last_counted_stats")
         return {f: getattr(s, f) for f, _ in LcCountedStats._fields_}
+
+    def last_witness_stats(self):
+        """lc_last_witness_stats: the witness search's share of the last call
+        (LC_FLAG_SEARCH_WITNESS), summed over its devices."""
+        s = LcWitnessStats()
+        rc = lib().lc_last_witness_stats(self._h, ctypes.byref(s))
+        if rc != 0:
+            raise LcError(rc, "lc_last_witness_stats")
+        return {f: getattr(s, f) for f, _ in LcWitnessStats._fields_}
 
     def device_stats(self):
         """lc_last_device_stats for every device of the last lc_check: one

@@ -38,7 +38,7 @@ arguments raise LcError, and jepsen's check-safe turns an exception into
 """
 import os
 
-from . import abi, diagnostics as D, history as H, linear_svg as LS, timeline as TL
+from . import abi, diagnostics as D, history as H, linear_svg as LS, timeline as TL, witness as W
 
 UNKNOWN = "unknown"
 # an invalid key the batched device search (lc_check_frontiers) could not
@@ -105,7 +105,7 @@ class RegisterChecker:
 
     def __init__(self, model=None, device_mask=0, max_configs_per_key=0, independent=True,
                  timeline_dir=None, time_budget_ms=0, whole_gpu=True, frontier_max_keys=1000,
-                 counted_classes=True):
+                 counted_classes=True, search_witness=False):
         self.model = model or VersionedRegister(0, None)
         # cap on the frontier re-searches one check() runs for diagnostics of
         # witnessed invalid keys (each is one key's search up to its failing
@@ -129,6 +129,14 @@ class RegisterChecker:
         # 1.1x for frontiers of a few thousand; keys with frontiers of tens
         # of thousands are quicker with counted_classes=False
         self.counted_classes = counted_classes
+        # a key a search tier decided (every version-less model's keys) gets
+        # no witness from the tiers; with search_witness the same call searches
+        # each such key once more, depth first, for a linearization
+        # (LC_FLAG_SEARCH_WITNESS), and its map gains "linearization" (its
+        # ops in that order) and "witness-certified" (the order checked
+        # against the definition on the host, witness.certify); an invalid
+        # key's "last-op" then comes from the order's last op
+        self.search_witness = search_witness
         self._ctx = None
         self._fx = None
 
@@ -158,7 +166,8 @@ class RegisterChecker:
         init = H.MUTEX_FREE if m.name == "mutex" else (0 if m.value is not None else H.LC_NIL)
         o = abi.default_opts(self.max_configs_per_key, m.version, init,
                              flags=(abi.LC_FLAG_WHOLE_GPU if self.whole_gpu else 0) |
-                             (abi.LC_FLAG_COUNTED_CLASSES if self.counted_classes else 0),
+                             (abi.LC_FLAG_COUNTED_CLASSES if self.counted_classes else 0) |
+                             (abi.LC_FLAG_SEARCH_WITNESS if self.search_witness else 0),
                              time_budget_ms=self.time_budget_ms)
         # the drop-in's call (ABI 5): 16-byte records when every value id
         # fits 15 bits, else 24-byte ones — what crosses PCIe (the JVM shim
@@ -242,7 +251,18 @@ class RegisterChecker:
                     out["previous-ok"] = D.previous_ok(done[i], int(r["fail_prefix_end"]))
                 if err is not None:
                     out["configs-error"] = err
-            elif v == UNKNOWN:
+            if self.search_witness and kind[i] in (abi.LC_WITNESS_ORDER_FULL,
+                                                   abi.LC_WITNESS_ORDER_PREFIX):
+                recs = ops[key_off[i]:key_off[i + 1]]
+                w = wit[key_off[i]:key_off[i + 1]]
+                lin = [done[i][j]["completion"] or done[i][j]["invoke"] for j in W.order(recs, w)]
+                out["linearization"] = lin
+                out["witness-certified"] = W.certify(recs, w, int(kind[i]),
+                                                     cut=int(r["fail_prefix_end"]) - 1,
+                                                     init=(m.version, init))
+                if v is False and lin and "last-op" not in out:
+                    out["last-op"] = lin[-1]
+            if v == UNKNOWN:
                 # the Clojure shim's keys (mi355x.clj): :cause and :error
                 cause = abi.REASONS.get(int(r["reason"]), int(r["reason"]))
                 out["cause"] = cause

@@ -58,6 +58,9 @@
 (def ^:const LC_NIL -1)
 (def ^:const LC_FLAG_WHOLE_GPU 8)  ; include/lincheck.h
 (def ^:const LC_FLAG_COUNTED_CLASSES 32)
+(def ^:const LC_FLAG_SEARCH_WITNESS 64)   ; additive to ABI 5: looked up as lc_last_witness_stats
+(def ^:const LC_WITNESS_ORDER_FULL 3)
+(def ^:const LC_WITNESS_ORDER_PREFIX 4)
 (def ^:const LC_INF Long/MAX_VALUE)
 (def ^:const op-bytes 48)      ; lc_op (the frontier searches)
 (def ^:const op32-bytes 24)    ; lc_op32 (lc_check32, ABI 4)
@@ -335,6 +338,44 @@
            path)
          (take 10)
          vec)))
+
+;; ---- LC_FLAG_SEARCH_WITNESS: the order a search-decided key comes back with
+;; (witness.py restates the same)
+
+(defn- witness-order
+  "Record indices in rank order (witness[r] = rank, -1 = left out)."
+  [witness]
+  (->> (map-indexed vector witness) (filter #(>= (second %) 0)) (sort-by second) (mapv first)))
+
+(defn- certify-order
+  "Is witness (an int per record) a linearization of records [f v e ver call
+  ret] at event cut (nil: the whole history), from the definition
+  (include/lincheck.h, lc_aux): ranks 0 .. L-1 each once; a record called
+  after cut left out and one returned by it ranked; every step legal from
+  [version value] (register.clj:60-96); every op returning after the largest
+  call among the ops ranked before it."
+  [records witness cut [v0 x0]]
+  (let [cut   (if (nil? cut) (dec LC_INF) cut)
+        order (witness-order witness)
+        ranks (map #(nth witness %) order)]
+    (and (= (count records) (count witness))
+         (= ranks (range (count order)))
+         (every? (fn [[[_ _ _ _ call ret] w]]
+                   (if (neg? w) (> ret cut) (<= call cut)))
+                 (map vector records witness))
+         (loop [is order, ver v0, val x0, latest nil]
+           (if-let [i (first is)]
+             (let [[f v e opver call ret] (nth records i)]
+               (cond
+                 (and latest (<= ret latest)) false
+                 (= f 0) (and (or (= opver LC_NIL) (= opver ver))
+                              (or (= v LC_NIL) (= v val))
+                              (recur (rest is) ver val (if latest (max latest call) call)))
+                 (#{1 2} f) (and (or (= opver LC_NIL) (= opver (inc ver)))
+                                 (or (= f 1) (= e val))
+                                 (recur (rest is) (inc ver) v (if latest (max latest call) call)))
+                 :else false))
+             true)))))
 
 (defn- previous-ok [done fail-ret]
   (let [oks (filter #(and (= :ok (:type (:completion %))) (< (:ret %) fail-ret)) done)]
@@ -619,16 +660,30 @@
                                                  wa (merge wa (select-keys fa [:configs-error]))
                                                  :else fa)))
                    (= v :unknown) (assoc :cause (reasons reason reason)
-                                         :error [:lincheck-reason (reasons reason reason)]))]))))))
+                                         :error [:lincheck-reason (reasons reason reason)])
+                   ;; LC_FLAG_SEARCH_WITNESS: the order of a key a search tier
+                   ;; decided, and its check against the definition
+                   (#{LC_WITNESS_ORDER_FULL LC_WITNESS_ORDER_PREFIX} (.getInt kind (* 4 ki)))
+                   ((fn [m]
+                      (let [w   (vec (.getIntArray wit (* 4 k0) (count d)))
+                            lin (mapv #(op-map (nth d %)) (witness-order w))]
+                        (cond-> (assoc m
+                                       :linearization lin
+                                       :witness-certified
+                                       (certify-order (first (key-records model d)) w
+                                                      (when (false? v) (dec fail-at))
+                                                      [0 (if (= model :mutex) 0 LC_NIL)]))
+                          (and (false? v) (seq lin) (not (:last-op m)))
+                          (assoc :last-op (peek lin)))))))]))))))
 
 (defn linearizable
   "(checker/linearizable {:model m}) over the whole history, for the knossos
   models this library packs: opts :model one of :versioned-register,
   :cas-register, :register, :mutex.  The lock workload's checker
   (lock.clj:243-244) becomes (linearizable {:model :mutex})."
-  [{:keys [model max-configs-per-key time-budget-ms whole-gpu? counted-classes?]
+  [{:keys [model max-configs-per-key time-budget-ms whole-gpu? counted-classes? search-witness?]
     :or {model :versioned-register max-configs-per-key 0 time-budget-ms 0 whole-gpu? true
-         counted-classes? true}}]
+         counted-classes? true search-witness? false}}]
   (reify checker/Checker
     (check [_ test history _opts]
       (let [ops (filterv client-op? history)]
@@ -636,7 +691,8 @@
           {:valid? true :analyzer :mi355x}
           (get (check-keys model max-configs-per-key time-budget-ms
                            (bit-or (if whole-gpu? LC_FLAG_WHOLE_GPU 0)
-                                   (if counted-classes? LC_FLAG_COUNTED_CLASSES 0))
+                                   (if counted-classes? LC_FLAG_COUNTED_CLASSES 0)
+                                   (if search-witness? LC_FLAG_SEARCH_WITNESS 0))
                            {nil ops}) nil))))))
 
 (defn- render-linear!
@@ -681,11 +737,17 @@
   ops were open at once is searched again inside the call with its crashed
   writes/CAS counted per class, LC_FLAG_COUNTED_CLASSES, before the whole-GPU
   search; the same results, much sooner for many small-frontier keys, slower
-  for keys with frontiers of tens of thousands of configurations)."
+  for keys with frontiers of tens of thousands of configurations),
+  :search-witness? (default false: with it a key a search tier decided is
+  searched once more, depth first, for a linearization,
+  LC_FLAG_SEARCH_WITNESS; its map gains :linearization, its ops in that
+  order, and :witness-certified, the order checked here against the
+  definition; an invalid key without a :last-op takes the order's last op)."
   ([] (checker {}))
-  ([{:keys [max-configs-per-key model timeline? time-budget-ms whole-gpu? counted-classes?]
+  ([{:keys [max-configs-per-key model timeline? time-budget-ms whole-gpu? counted-classes?
+            search-witness?]
      :or {max-configs-per-key 0 model :versioned-register timeline? true time-budget-ms 0
-          whole-gpu? true counted-classes? true}}]
+          whole-gpu? true counted-classes? true search-witness? false}}]
    (reify checker/Checker
      (check [_ test history opts]
        (let [subs (subhistories history)]
@@ -693,7 +755,8 @@
            {:valid? true :results {} :failures []}
            (let [linear  (check-keys model max-configs-per-key time-budget-ms
                                      (bit-or (if whole-gpu? LC_FLAG_WHOLE_GPU 0)
-                                             (if counted-classes? LC_FLAG_COUNTED_CLASSES 0))
+                                             (if counted-classes? LC_FLAG_COUNTED_CLASSES 0)
+                                             (if search-witness? LC_FLAG_SEARCH_WITNESS 0))
                                      subs)
                  results (into (array-map)
                                (for [[k r] linear]

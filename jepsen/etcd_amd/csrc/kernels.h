@@ -301,6 +301,44 @@ hipError_t launch_counted_frontier(const lc_op *d_ops, const int64_t *d_key_off,
                                    int32_t *d_ovf_out, int32_t *d_n_ovf_out, int32_t *d_next,
                                    int last_tier, int value_only, hipStream_t stream);
 
+// Witness search (LC_FLAG_SEARCH_WITNESS; witness_search.hip): a depth-first
+// search with a cache of dead ends over the keys that are decided but have
+// witness kind NONE, one wavefront per key; its stack is the linearization
+// (LC_WITNESS_ORDER_FULL / _PREFIX).  launch_witness_compact lists those keys
+// in d_keys (st->n_list; st->max_len: the longest, in records; *d_st zero at
+// launch); launch_witness_search claims them from st->next and, for every
+// key it finds an order for, writes the ranks into the key's records of
+// d_witness and its kind.  A key it gives up on (p.budget search steps,
+// p.time_ticks, a key longer than max_n: n_budget; a 65th open op: n_window)
+// keeps what it had.  Workspace: witness_ws_bytes(n_waves, max_n), no initial
+// contents.
+struct WitnessStatus {
+  int32_t n_list, max_len, next;
+  int32_t n_found, n_budget, n_window;
+  unsigned long long nodes, cache_hits;
+};
+// Search steps per key at most, whatever lc_opts.max_configs_per_key says: a
+// wavefront that spends them all has run for about 100 ms (the
+// measured rate).
+constexpr int64_t kWitnessNodeCap = 1 << 16;
+constexpr int kWitnessWaves = 1024;     // one per SIMD
+// dead-end cache per wave: 128-byte buckets of five nodes (the first capacity
+// of the HBM tiers' ladder, 2^14 configurations, and a quarter more)
+constexpr int kWitnessBuckets = 4096;
+__host__ __device__ inline int64_t witness_round(int64_t max_n) { return (max_n + 127) & ~int64_t(127); }
+// per wave: the cache, then per record a frame (32 B), an event (16 B), a slot
+__host__ __device__ inline size_t witness_wave_bytes(int64_t max_n) {
+  return (size_t)kWitnessBuckets * 128 + (size_t)witness_round(max_n) * (32 + 16 + 1);
+}
+size_t witness_ws_bytes(int n_waves, int64_t max_n);
+hipError_t launch_witness_compact(const lc_key_result *d_out, const int32_t *d_kind,
+                                  const int64_t *d_key_off, int64_t n_keys, int32_t *d_keys,
+                                  WitnessStatus *d_st, hipStream_t stream);
+hipError_t launch_witness_search(const lc_op *d_ops, const int64_t *d_key_off, const int32_t *d_keys,
+                                 int32_t n_list, const KParams &p, const lc_key_result *d_out,
+                                 int32_t *d_witness, int32_t *d_witness_kind, void *d_ws, int n_waves,
+                                 int64_t max_n, WitnessStatus *d_st, hipStream_t stream);
+
 // Gap tier (gap_tier.hip): version-pinned keys with crashed writes/CAS are
 // decided by matching gaps to optional ops; keys it cannot decide are
 // appended to d_pass_keys (status->n_jit2).  A call runs two kinds of launch

@@ -59,6 +59,9 @@ constexpr int kHbmTiers = 3;
 constexpr size_t kFxEngines = 4;  // LC_FLAG_WHOLE_GPU: oversized keys searched at once
 constexpr int64_t kHbmCap[kHbmTiers] = {1 << 14, 1 << 18, 1 << 21};
 constexpr int kHbmWaves[kHbmTiers] = {2048, 128, 16};
+// LC_FLAG_SEARCH_WITNESS: the witness search's workspace at most (512 KB of
+// cache per wave, 49 B per record of the longest listed key)
+constexpr size_t kWitnessWsBytes = size_t(2) << 30;
 // HBM tier lists up to these sizes get a workgroup of 16 (4) wavefronts per
 // key; longer lists a wavefront per key.  Measured (tools/hbm_probe.py,
 // DESIGN.md §4): 16 wins on 512 crash-heavy keys (4.9 s vs 13.1 s with 4,
@@ -128,6 +131,7 @@ struct Dev {
   Buf<int32_t> d_cws;           // certificate workspace
   Buf<char> d_ops32;            // copy pipeline: lc_check32 / lc_check16's staging records
   Buf<int64_t> d_base;          // ... and the keys' bases
+  Buf<lcdev::WitnessStatus> d_wst;  // LC_FLAG_SEARCH_WITNESS: the stage's status words
 
   // ---- events ----
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
@@ -196,6 +200,7 @@ struct Dev {
   int64_t n_gap = 0, n_jit = 0, n_hbm = 0;
   int malformed = 0;
   lc_counted_stats counted{};               // this device's share of lc_last_counted_stats
+  lc_witness_stats wit{};                   // this device's share of lc_last_witness_stats
   lc_device_stats last{};                   // this device's share of the last lc_check
   double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
   // this device's share of lc_last_totals: written only by the device's own
@@ -680,6 +685,7 @@ int begin_call(Run &r) {
   d.n_hbm = d.n_jit = d.n_gap = 0;
   d.malformed = 0;
   d.counted = lc_counted_stats{};
+  d.wit = lc_witness_stats{};
   if (r.n_keys <= 0) return 0;
   if (r.n_keys > INT32_MAX) {
     set_err(c, "lc_check: more than 2^31-1 keys in one call");
@@ -1190,6 +1196,59 @@ int counted_tier(Run &r) {
   return 0;
 }
 
+// LC_FLAG_SEARCH_WITNESS: the keys that are decided but still have witness
+// kind NONE (a search tier decided them) are listed on the device from d_out
+// and the kind array and searched depth first for a linearization (kernels.h
+// launch_witness_search), which becomes their witness; nothing else of the
+// call's outputs changes.  Runs last, with its own status words (d_wst: the
+// d_status invariant is not its concern) and, while it runs, the HBM tiers'
+// workspace; e1 / e2 are free again.
+int witness_stage(Run &r) {
+  if (!(r.flags & LC_FLAG_SEARCH_WITNESS) || !r.want_wit) return 0;
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  if (int rc = ensure(c, d.d_wst, sizeof(lcdev::WitnessStatus))) return rc;
+  lcdev::WitnessStatus ws{};
+  auto read_ws = [&]() -> int {
+    HIP_TRY(c, hipMemcpyAsync(&ws, d.d_wst.p, sizeof(ws), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return 0;
+  };
+  int32_t *list = d.d_ovf.p;
+  HIP_TRY(c, hipMemsetAsync(d.d_wst.p, 0, sizeof(lcdev::WitnessStatus), st));
+  HIP_TRY(c, hipEventRecord(d.e1, st));
+  HIP_TRY(c, lcdev::launch_witness_compact(r.d_out, r.ao.kind, r.d_off, r.n_keys, list, d.d_wst.p, st));
+  if (int e = read_ws()) return e;
+  const int32_t n_list = ws.n_list;
+  d.wit.n_keys = n_list;
+  if (n_list <= 0) return 0;
+  // one wave per SIMD at most, and as many as kWitnessWsBytes of workspace
+  // hold; a key longer than that much workspace for one wave is not searched
+  int64_t max_n = std::max<int64_t>(ws.max_len, 1);
+  while (lcdev::witness_wave_bytes(max_n) > kWitnessWsBytes) max_n /= 2;
+  const int waves = (int)std::min<int64_t>(
+      std::min<int64_t>(n_list, lcdev::kWitnessWaves),
+      std::max<int64_t>(1, (int64_t)(kWitnessWsBytes / lcdev::witness_wave_bytes(max_n))));
+  if (int rc = ensure(c, d.d_ws, lcdev::witness_ws_bytes(waves, max_n))) return rc;
+  lcdev::KParams p = r.p;
+  p.budget = std::min<int64_t>(p.budget, lcdev::kWitnessNodeCap);
+  HIP_TRY(c, lcdev::launch_witness_search(r.d_ops, r.d_off, list, n_list, p, r.d_out, r.ao.wit, r.ao.kind,
+                                          d.d_ws.p, waves, max_n, d.d_wst.p, st));
+  HIP_TRY(c, hipEventRecord(d.e2, st));
+  if (int e = read_ws()) return e;
+  float ms = 0;
+  HIP_TRY(c, hipEventElapsedTime(&ms, d.e1, d.e2));
+  d.wit.kernel_ms = ms;
+  d.wit.n_found = ws.n_found;
+  d.wit.n_budget = ws.n_budget;
+  d.wit.n_window = ws.n_window;
+  d.wit.nodes = (int64_t)ws.nodes;
+  d.wit.cache_hits = (int64_t)ws.cache_hits;
+  d.tot.kernel_ms += ms;
+  return 0;
+}
+
 // The later tiers ran: d_status back to zero (the invariant between calls),
 // the call's totals.
 int end_call(Run &r) {
@@ -1234,13 +1293,14 @@ int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int6
     // (the host has read it), not in front of the next call's
     if (r.light) HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
     d.status_dirty = false;
-    return 0;
+    return witness_stage(r);  // (a gap-tier decision may have come without a witness)
   }
   if (int e = gap_tier(r)) return e;
   if (int e = search_tier(r)) return e;
   if (int e = hbm_tiers(r)) return e;
   if (int e = counted_tier(r)) return e;
-  return end_call(r);
+  if (int e = end_call(r)) return e;
+  return witness_stage(r);
 }
 
 
@@ -1628,7 +1688,10 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
   };
   c->stats = lc_stats{};
   c->prof = lc_call_profile{};
-  for (Dev &d : c->devs) d.counted = lc_counted_stats{};  // (a device without keys runs nothing)
+  for (Dev &d : c->devs) {  // (a device without keys runs nothing)
+    d.counted = lc_counted_stats{};
+    d.wit = lc_witness_stats{};
+  }
   if (n_keys < 0 || (n_keys > 0 && (!ops || !key_off || !out))) {
     set_err(c, "lc_check: null buffer or negative n_keys");
     return -EINVAL;
@@ -2009,7 +2072,10 @@ int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const 
                  void *stream, const lc_aux *aux) {
   const auto t0 = std::chrono::steady_clock::now();
   c->stats = lc_stats{};
-  for (Dev &d : c->devs) d.counted = lc_counted_stats{};
+  for (Dev &d : c->devs) {
+    d.counted = lc_counted_stats{};
+    d.wit = lc_witness_stats{};
+  }
   if (n_keys < 0 || (n_keys > 0 && (!ops || !d_key_off || !d_out))) {
     set_err(c, std::string(who) + ": null buffer or negative n_keys");
     return -EINVAL;
@@ -2374,7 +2440,7 @@ void lc_close(lc_ctx *c) {
     for (void *b : std::initializer_list<void *>{
              d.d_ops.p, d.d_off.p, d.d_out.p, d.d_ovf.p, d.d_ovf2.p, d.d_jit.p, d.d_flags.p, d.d_jit2.p,
              d.d_gap2.p, d.d_gws.p, d.d_cex.p, d.d_ws.p, d.d_wit.p, d.d_kind.p, d.d_cert.p, d.d_cset.p,
-             d.d_cws.p, d.d_ops32.p, d.d_base.p})
+             d.d_cws.p, d.d_ops32.p, d.d_base.p, d.d_wst.p})
       if (b) (void)hipFree(b);
     if (d.d_status) (void)hipFree(d.d_status);
     if (d.h_status) (void)hipHostFree(d.h_status);
@@ -2432,6 +2498,22 @@ int lc_last_counted_stats(lc_ctx *c, lc_counted_stats *out) {
     s.n_decided += d.counted.n_decided;
     s.n_unfit += d.counted.n_unfit;
     s.kernel_ms += d.counted.kernel_ms;
+  }
+  *out = s;
+  return 0;
+}
+
+int lc_last_witness_stats(lc_ctx *c, lc_witness_stats *out) {
+  if (!c || !out) return -EINVAL;
+  lc_witness_stats s{};
+  for (const Dev &d : c->devs) {
+    s.n_keys += d.wit.n_keys;
+    s.n_found += d.wit.n_found;
+    s.n_budget += d.wit.n_budget;
+    s.n_window += d.wit.n_window;
+    s.nodes += d.wit.nodes;
+    s.cache_hits += d.wit.cache_hits;
+    s.kernel_ms += d.wit.kernel_ms;
   }
   *out = s;
   return 0;
