@@ -2364,6 +2364,9 @@ __device__ bool first_failure(int64_t key, int n, const lc_op *__restrict__ kops
   uint32_t *NR = reinterpret_cast<uint32_t *>(lds_dyn);  // ops' returns by need, then N(p)
   if (4 * tid < n) reinterpret_cast<uint4 *>(MR)[tid] = make_uint4(kNever, kNever, kNever, kNever);
   if (4 * tid <= n + 1) reinterpret_cast<uint4 *>(NR)[tid] = make_uint4(kNever, kNever, kNever, kNever);
+  // (a key of kFastMax records: NR[n] — position n-1's holder, reads of
+  // version n — lies past the last thread's four entries)
+  if (tid == 0 && n == kFastMax) NR[kFastMax] = kNever;
   __syncthreads();
   uint32_t t = kNever;  // this thread's earliest violation
   // step 1: each position's earliest-returning mutation; returns by need
@@ -2409,6 +2412,8 @@ __device__ bool first_failure(int64_t key, int n, const lc_op *__restrict__ kops
   uint32_t na = umin(umin(nr4.x, nr4.y), umin(nr4.z, nr4.w));
   uint32_t ba = umin(umin(b4.x, b4.y), umin(b4.z, b4.w));
   suffix_min2_excl(na, ba, s);  // (its barrier also orders step 2's stores)
+  // NR[kFastMax] belongs to no thread's four: every suffix includes it
+  if (n == kFastMax) na = umin(na, NR[kFastMax]);
   if (4 * tid <= n + 1) {
     // N(p) = min NR[p+1 ..]; Uh(p) = min B[p ..]
     const uint32_t n3 = na, n2 = umin(n3, nr4.w), n1 = umin(n2, nr4.z), n0 = umin(n1, nr4.y);
@@ -2885,6 +2890,9 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
       else if (k < n) hole |= (oo[j] != 0xFFFF) | ((k > M) & (aa[j] != 0));
       else if (k == n) hole |= (k > M) & (aa[j] != 0);
     }
+    // (a key of kFastMax records: k == n has no thread, thread 0 takes a
+    // read of version n past the last mutation)
+    if (tid == 0 && n == kFastMax) hole |= (n > M) & (s.A[kFastMax] != 0);
   }
   FP_T(3);
   if (timing_fails(s, M, tid)) hole = 1;
