@@ -123,6 +123,19 @@ typedef struct lc_opts {
                                    LC_FLAG_WHOLE_GPU are not searched.  Without the flag every
                                    output is what it was.  Callers detect the feature by
                                    looking up lc_last_witness_stats (LC_ABI_VERSION stays 5) */
+#define LC_FLAG_COUNTED_WITNESS 128 /* only together with LC_FLAG_SEARCH_WITNESS (alone it is inert):
+                                   a key that search gives up on because more than LC_MAX_WINDOW ops
+                                   are open at once (lc_witness_stats.n_window: the keys the counted
+                                   tier decides) is searched once more with its crashed writes/CAS
+                                   counted per class by lc_counted_plan's rule instead of holding a
+                                   slot each.  An order found is written with the same kinds and in
+                                   the same format, LC_WITNESS_ORDER_FULL / LC_WITNESS_ORDER_PREFIX;
+                                   a crashed read is never ranked.  A key beyond the layout rule, or
+                                   with more than its `slots` other ops open at once, keeps kind NONE
+                                   (lc_counted_witness_stats.n_unfit).  lc_witness_stats and every
+                                   lc_key_result are what they are without the flag.  Callers detect
+                                   the feature by looking up lc_last_counted_witness_stats
+                                   (LC_ABI_VERSION stays 5) */
 
 /* Verdicts: Knossos :valid? true / false / :unknown. */
 #define LC_VALID    1
@@ -553,7 +566,8 @@ const char *lc_build_id(void);
 
 /* LC_FLAG_COUNTED_CLASSES: lc_counted_plan, lc_last_counted_stats */
 #include "lincheck_counted.h"
-/* LC_FLAG_SEARCH_WITNESS: lc_last_witness_stats */
+/* LC_FLAG_SEARCH_WITNESS: lc_last_witness_stats; LC_FLAG_COUNTED_WITNESS:
+ * lc_last_counted_witness_stats */
 #include "lincheck_witness.h"
 
 #endif /* LINCHECK_H */

@@ -43,6 +43,7 @@ LC_FLAG_WHOLE_GPU = 8
 LC_FLAG_NO_TIMING = 16
 LC_FLAG_COUNTED_CLASSES = 32
 LC_FLAG_SEARCH_WITNESS = 64
+LC_FLAG_COUNTED_WITNESS = 128  # only with LC_FLAG_SEARCH_WITNESS
 LC_COUNTED_MAX_CLASSES = 16
 LC_WITNESS_NONE, LC_WITNESS_FULL, LC_WITNESS_PREFIX = 0, 1, 2
 LC_WITNESS_ORDER_FULL, LC_WITNESS_ORDER_PREFIX = 3, 4  # LC_FLAG_SEARCH_WITNESS (witness.py)
@@ -115,6 +116,13 @@ class LcCountedStats(ctypes.Structure):
 class LcWitnessStats(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("n_found", ctypes.c_int64),
                 ("n_budget", ctypes.c_int64), ("n_window", ctypes.c_int64),
+                ("nodes", ctypes.c_int64), ("cache_hits", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
+class LcCountedWitnessStats(ctypes.Structure):
+    _fields_ = [("n_keys", ctypes.c_int64), ("n_found", ctypes.c_int64),
+                ("n_budget", ctypes.c_int64), ("n_unfit", ctypes.c_int64),
                 ("nodes", ctypes.c_int64), ("cache_hits", ctypes.c_int64),
                 ("kernel_ms", ctypes.c_double)]
 
@@ -234,6 +242,9 @@ def lib():
         if hasattr(L, "lc_last_witness_stats"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
             L.lc_last_witness_stats.argtypes = [vp, ctypes.POINTER(LcWitnessStats)]
             L.lc_last_witness_stats.restype = ctypes.c_int
+        if hasattr(L, "lc_last_counted_witness_stats"):  # (the same)
+            L.lc_last_counted_witness_stats.argtypes = [vp, ctypes.POINTER(LcCountedWitnessStats)]
+            L.lc_last_counted_witness_stats.restype = ctypes.c_int
         if hasattr(L, "lc_check_frontiers_counted"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
             L.lc_check_frontiers_counted.argtypes = [vp, p, p, i64, p, ctypes.POINTER(LcOpts), p, i32,
                                                      p, p, p, i64]
@@ -380,6 +391,16 @@ class Context:
         if rc != 0:
             raise LcError(rc, "lc_last_witness_stats")
         return {f: getattr(s, f) for f, _ in LcWitnessStats._fields_}
+
+    def last_counted_witness_stats(self):
+        """lc_last_counted_witness_stats: the share of the counted witness
+        stage (LC_FLAG_SEARCH_WITNESS | LC_FLAG_COUNTED_WITNESS) of the last
+        call, summed over its devices."""
+        s = LcCountedWitnessStats()
+        rc = lib().lc_last_counted_witness_stats(self._h, ctypes.byref(s))
+        if rc != 0:
+            raise LcError(rc, "lc_last_counted_witness_stats")
+        return {f: getattr(s, f) for f, _ in LcCountedWitnessStats._fields_}
 
     def device_stats(self):
         """lc_last_device_stats for every device of the last lc_check: one

@@ -105,7 +105,7 @@ class RegisterChecker:
 
     def __init__(self, model=None, device_mask=0, max_configs_per_key=0, independent=True,
                  timeline_dir=None, time_budget_ms=0, whole_gpu=True, frontier_max_keys=1000,
-                 counted_classes=True, search_witness=False):
+                 counted_classes=True, search_witness=False, counted_witness=True):
         self.model = model or VersionedRegister(0, None)
         # cap on the frontier re-searches one check() runs for diagnostics of
         # witnessed invalid keys (each is one key's search up to its failing
@@ -137,8 +137,21 @@ class RegisterChecker:
         # against the definition on the host, witness.certify); an invalid
         # key's "last-op" then comes from the order's last op
         self.search_witness = search_witness
+        # ... and a key that search leaves because more than 64 ops are open
+        # at once (the crash-heavy keys the counted tier decides) is searched
+        # once more with its crashed writes/CAS counted per class
+        # (LC_FLAG_COUNTED_WITNESS): the same two entries for those keys.
+        # Means something only with search_witness.
+        self.counted_witness = counted_witness
         self._ctx = None
         self._fx = None
+
+    def _flags(self):
+        """lc_opts.flags of this checker's calls."""
+        return (abi.LC_FLAG_WHOLE_GPU if self.whole_gpu else 0) | \
+            (abi.LC_FLAG_COUNTED_CLASSES if self.counted_classes else 0) | \
+            (abi.LC_FLAG_SEARCH_WITNESS if self.search_witness else 0) | \
+            (abi.LC_FLAG_COUNTED_WITNESS if self.search_witness and self.counted_witness else 0)
 
     def _context(self):
         if self._ctx is None:
@@ -164,10 +177,7 @@ class RegisterChecker:
         # the initial value is interned first in every key (id 0); the mutex
         # starts free (id MUTEX_FREE)
         init = H.MUTEX_FREE if m.name == "mutex" else (0 if m.value is not None else H.LC_NIL)
-        o = abi.default_opts(self.max_configs_per_key, m.version, init,
-                             flags=(abi.LC_FLAG_WHOLE_GPU if self.whole_gpu else 0) |
-                             (abi.LC_FLAG_COUNTED_CLASSES if self.counted_classes else 0) |
-                             (abi.LC_FLAG_SEARCH_WITNESS if self.search_witness else 0),
+        o = abi.default_opts(self.max_configs_per_key, m.version, init, flags=self._flags(),
                              time_budget_ms=self.time_budget_ms)
         # the drop-in's call (ABI 5): 16-byte records when every value id
         # fits 15 bits, else 24-byte ones — what crosses PCIe (the JVM shim

@@ -59,6 +59,7 @@
 (def ^:const LC_FLAG_WHOLE_GPU 8)  ; include/lincheck.h
 (def ^:const LC_FLAG_COUNTED_CLASSES 32)
 (def ^:const LC_FLAG_SEARCH_WITNESS 64)   ; additive to ABI 5: looked up as lc_last_witness_stats
+(def ^:const LC_FLAG_COUNTED_WITNESS 128) ; only with LC_FLAG_SEARCH_WITNESS; lc_last_counted_witness_stats
 (def ^:const LC_WITNESS_ORDER_FULL 3)
 (def ^:const LC_WITNESS_ORDER_PREFIX 4)
 (def ^:const LC_INF Long/MAX_VALUE)
@@ -681,9 +682,10 @@
   models this library packs: opts :model one of :versioned-register,
   :cas-register, :register, :mutex.  The lock workload's checker
   (lock.clj:243-244) becomes (linearizable {:model :mutex})."
-  [{:keys [model max-configs-per-key time-budget-ms whole-gpu? counted-classes? search-witness?]
+  [{:keys [model max-configs-per-key time-budget-ms whole-gpu? counted-classes? search-witness?
+           counted-witness?]
     :or {model :versioned-register max-configs-per-key 0 time-budget-ms 0 whole-gpu? true
-         counted-classes? true search-witness? false}}]
+         counted-classes? true search-witness? false counted-witness? true}}]
   (reify checker/Checker
     (check [_ test history _opts]
       (let [ops (filterv client-op? history)]
@@ -692,7 +694,8 @@
           (get (check-keys model max-configs-per-key time-budget-ms
                            (bit-or (if whole-gpu? LC_FLAG_WHOLE_GPU 0)
                                    (if counted-classes? LC_FLAG_COUNTED_CLASSES 0)
-                                   (if search-witness? LC_FLAG_SEARCH_WITNESS 0))
+                                   (if search-witness? LC_FLAG_SEARCH_WITNESS 0)
+                                   (if (and search-witness? counted-witness?) LC_FLAG_COUNTED_WITNESS 0))
                            {nil ops}) nil))))))
 
 (defn- render-linear!
@@ -742,12 +745,17 @@
   searched once more, depth first, for a linearization,
   LC_FLAG_SEARCH_WITNESS; its map gains :linearization, its ops in that
   order, and :witness-certified, the order checked here against the
-  definition; an invalid key without a :last-op takes the order's last op)."
+  definition; an invalid key without a :last-op takes the order's last op),
+  :counted-witness? (default true, means something only with
+  :search-witness?: a key that search leaves because more than 64 ops are
+  open at once — the crash-heavy keys the counted tier decides — is searched
+  once more with its crashed writes/CAS counted per class,
+  LC_FLAG_COUNTED_WITNESS, and gets the same two entries)."
   ([] (checker {}))
   ([{:keys [max-configs-per-key model timeline? time-budget-ms whole-gpu? counted-classes?
-            search-witness?]
+            search-witness? counted-witness?]
      :or {max-configs-per-key 0 model :versioned-register timeline? true time-budget-ms 0
-          whole-gpu? true counted-classes? true search-witness? false}}]
+          whole-gpu? true counted-classes? true search-witness? false counted-witness? true}}]
    (reify checker/Checker
      (check [_ test history opts]
        (let [subs (subhistories history)]
@@ -756,7 +764,8 @@
            (let [linear  (check-keys model max-configs-per-key time-budget-ms
                                      (bit-or (if whole-gpu? LC_FLAG_WHOLE_GPU 0)
                                              (if counted-classes? LC_FLAG_COUNTED_CLASSES 0)
-                                             (if search-witness? LC_FLAG_SEARCH_WITNESS 0))
+                                             (if search-witness? LC_FLAG_SEARCH_WITNESS 0)
+                                             (if (and search-witness? counted-witness?) LC_FLAG_COUNTED_WITNESS 0))
                                      subs)
                  results (into (array-map)
                                (for [[k r] linear]

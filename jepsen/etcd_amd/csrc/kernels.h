@@ -310,12 +310,18 @@ hipError_t launch_counted_frontier(const lc_op *d_ops, const int64_t *d_key_off,
 // key it finds an order for, writes the ranks into the key's records of
 // d_witness and its kind.  A key it gives up on (p.budget search steps,
 // p.time_ticks, a key longer than max_n: n_budget; a 65th open op: n_window)
-// keeps what it had.  Workspace: witness_ws_bytes(n_waves, max_n), no initial
-// contents.
+// keeps what it had; the n_window keys are also listed in d_window_keys
+// (st->n_wlist) for the counted stage below.  Workspace:
+// witness_ws_bytes(n_waves, max_n), no initial contents.
 struct WitnessStatus {
   int32_t n_list, max_len, next;
   int32_t n_found, n_budget, n_window;
   unsigned long long nodes, cache_hits;
+  // the counted stage (below): keys launch_witness_search listed for it, the
+  // next entry to claim, its outcomes
+  int32_t n_wlist, cw_next;
+  int32_t cw_found, cw_budget, cw_unfit, pad;
+  unsigned long long cw_nodes, cw_hits;
 };
 // Search steps per key at most, whatever lc_opts.max_configs_per_key says: a
 // wavefront that spends them all has run for about 100 ms (the
@@ -337,7 +343,27 @@ hipError_t launch_witness_compact(const lc_key_result *d_out, const int32_t *d_k
 hipError_t launch_witness_search(const lc_op *d_ops, const int64_t *d_key_off, const int32_t *d_keys,
                                  int32_t n_list, const KParams &p, const lc_key_result *d_out,
                                  int32_t *d_witness, int32_t *d_witness_kind, void *d_ws, int n_waves,
-                                 int64_t max_n, WitnessStatus *d_st, hipStream_t stream);
+                                 int64_t max_n, WitnessStatus *d_st, int32_t *d_window_keys,
+                                 hipStream_t stream);
+
+// Counted witness stage (LC_FLAG_COUNTED_WITNESS; witness_search.hip): the
+// keys launch_witness_search gave up on at a 65th open op — it lists them in
+// d_window_keys (st->n_wlist; room for n_list entries) — searched again with
+// the crashed writes/CAS counted per class by the layout rule of counted.h
+// instead of holding a slot each.  Same search, bounds, outputs and claiming
+// (st->cw_next); outcomes in st->cw_found / cw_budget / cw_unfit (a key
+// outside the layout rule, or with more :ok ops open at once than it has
+// slots) / cw_nodes / cw_hits.  Workspace: witness_counted_ws_bytes(n_waves,
+// max_n), no initial contents: per wave the first stage's layout, then 4
+// bytes per record for the classes' member lists.
+__host__ __device__ inline size_t witness_counted_wave_bytes(int64_t max_n) {
+  return witness_wave_bytes(max_n) + (size_t)witness_round(max_n) * 4;
+}
+size_t witness_counted_ws_bytes(int n_waves, int64_t max_n);
+hipError_t launch_witness_counted(const lc_op *d_ops, const int64_t *d_key_off, const int32_t *d_keys,
+                                  int32_t n_list, const KParams &p, const lc_key_result *d_out,
+                                  int32_t *d_witness, int32_t *d_witness_kind, void *d_ws, int n_waves,
+                                  int64_t max_n, WitnessStatus *d_st, hipStream_t stream);
 
 // Gap tier (gap_tier.hip): version-pinned keys with crashed writes/CAS are
 // decided by matching gaps to optional ops; keys it cannot decide are

@@ -201,6 +201,7 @@ struct Dev {
   int malformed = 0;
   lc_counted_stats counted{};               // this device's share of lc_last_counted_stats
   lc_witness_stats wit{};                   // this device's share of lc_last_witness_stats
+  lc_counted_witness_stats cwit{};          // this device's share of lc_last_counted_witness_stats
   lc_device_stats last{};                   // this device's share of the last lc_check
   double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
   // this device's share of lc_last_totals: written only by the device's own
@@ -601,6 +602,10 @@ struct Run {
   int64_t n_direct = 0;  // keys the fast tier sent straight to d_jit2
   int32_t n_ovf = 0;     // keys the search tier leaves to the HBM tiers (d_ovf)
   hipEvent_t before_jit = nullptr;
+  // witness_stage: the keys it left at n_window (listed in d_ovf2), and the
+  // longest key of its own list, for counted_witness_stage
+  int32_t n_wlist = 0;
+  int64_t wit_max_len = 0;
   GapPlan early;  // the gap tier launched early (handoff), if it was
   bool early_launched = false;
 };
@@ -686,6 +691,7 @@ int begin_call(Run &r) {
   d.malformed = 0;
   d.counted = lc_counted_stats{};
   d.wit = lc_witness_stats{};
+  d.cwit = lc_counted_witness_stats{};
   if (r.n_keys <= 0) return 0;
   if (r.n_keys > INT32_MAX) {
     set_err(c, "lc_check: more than 2^31-1 keys in one call");
@@ -1234,9 +1240,11 @@ int witness_stage(Run &r) {
   lcdev::KParams p = r.p;
   p.budget = std::min<int64_t>(p.budget, lcdev::kWitnessNodeCap);
   HIP_TRY(c, lcdev::launch_witness_search(r.d_ops, r.d_off, list, n_list, p, r.d_out, r.ao.wit, r.ao.kind,
-                                          d.d_ws.p, waves, max_n, d.d_wst.p, st));
+                                          d.d_ws.p, waves, max_n, d.d_wst.p, d.d_ovf2.p, st));
   HIP_TRY(c, hipEventRecord(d.e2, st));
   if (int e = read_ws()) return e;
+  r.n_wlist = ws.n_wlist;
+  r.wit_max_len = ws.max_len;
   float ms = 0;
   HIP_TRY(c, hipEventElapsedTime(&ms, d.e1, d.e2));
   d.wit.kernel_ms = ms;
@@ -1245,6 +1253,47 @@ int witness_stage(Run &r) {
   d.wit.n_window = ws.n_window;
   d.wit.nodes = (int64_t)ws.nodes;
   d.wit.cache_hits = (int64_t)ws.cache_hits;
+  d.tot.kernel_ms += ms;
+  return 0;
+}
+
+// LC_FLAG_COUNTED_WITNESS (with LC_FLAG_SEARCH_WITNESS): the keys
+// witness_stage left at n_window (it listed them in d_ovf2) are searched
+// again with their crashed writes/CAS counted per class (kernels.h
+// launch_witness_counted).  Runs right behind witness_stage: its status words
+// (the stage's own are zero since witness_stage's memset), its workspace and
+// e1 / e2, which are free again.
+int counted_witness_stage(Run &r) {
+  if (!(r.flags & LC_FLAG_COUNTED_WITNESS) || !(r.flags & LC_FLAG_SEARCH_WITNESS) || !r.want_wit) return 0;
+  lc_ctx *c = r.c;
+  Dev &d = r.d;
+  hipStream_t st = r.st;
+  const int32_t n_list = r.n_wlist;
+  d.cwit.n_keys = n_list;
+  if (n_list <= 0) return 0;
+  int64_t max_n = std::max<int64_t>(r.wit_max_len, 1);
+  while (lcdev::witness_counted_wave_bytes(max_n) > kWitnessWsBytes) max_n /= 2;
+  const int waves = (int)std::min<int64_t>(
+      std::min<int64_t>(n_list, lcdev::kWitnessWaves),
+      std::max<int64_t>(1, (int64_t)(kWitnessWsBytes / lcdev::witness_counted_wave_bytes(max_n))));
+  if (int rc = ensure(c, d.d_ws, lcdev::witness_counted_ws_bytes(waves, max_n))) return rc;
+  lcdev::KParams p = r.p;
+  p.budget = std::min<int64_t>(p.budget, lcdev::kWitnessNodeCap);
+  HIP_TRY(c, hipEventRecord(d.e1, st));
+  HIP_TRY(c, lcdev::launch_witness_counted(r.d_ops, r.d_off, d.d_ovf2.p, n_list, p, r.d_out, r.ao.wit,
+                                           r.ao.kind, d.d_ws.p, waves, max_n, d.d_wst.p, st));
+  HIP_TRY(c, hipEventRecord(d.e2, st));
+  lcdev::WitnessStatus ws{};
+  HIP_TRY(c, hipMemcpyAsync(&ws, d.d_wst.p, sizeof(ws), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  float ms = 0;
+  HIP_TRY(c, hipEventElapsedTime(&ms, d.e1, d.e2));
+  d.cwit.kernel_ms = ms;
+  d.cwit.n_found = ws.cw_found;
+  d.cwit.n_budget = ws.cw_budget;
+  d.cwit.n_unfit = ws.cw_unfit;
+  d.cwit.nodes = (int64_t)ws.cw_nodes;
+  d.cwit.cache_hits = (int64_t)ws.cw_hits;
   d.tot.kernel_ms += ms;
   return 0;
 }
@@ -1293,14 +1342,16 @@ int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int6
     // (the host has read it), not in front of the next call's
     if (r.light) HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
     d.status_dirty = false;
-    return witness_stage(r);  // (a gap-tier decision may have come without a witness)
+    if (int e = witness_stage(r)) return e;  // (a gap-tier decision may have come without a witness)
+    return counted_witness_stage(r);
   }
   if (int e = gap_tier(r)) return e;
   if (int e = search_tier(r)) return e;
   if (int e = hbm_tiers(r)) return e;
   if (int e = counted_tier(r)) return e;
   if (int e = end_call(r)) return e;
-  return witness_stage(r);
+  if (int e = witness_stage(r)) return e;
+  return counted_witness_stage(r);
 }
 
 
@@ -1691,6 +1742,7 @@ int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *
   for (Dev &d : c->devs) {  // (a device without keys runs nothing)
     d.counted = lc_counted_stats{};
     d.wit = lc_witness_stats{};
+    d.cwit = lc_counted_witness_stats{};
   }
   if (n_keys < 0 || (n_keys > 0 && (!ops || !key_off || !out))) {
     set_err(c, "lc_check: null buffer or negative n_keys");
@@ -2075,6 +2127,7 @@ int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const 
   for (Dev &d : c->devs) {
     d.counted = lc_counted_stats{};
     d.wit = lc_witness_stats{};
+    d.cwit = lc_counted_witness_stats{};
   }
   if (n_keys < 0 || (n_keys > 0 && (!ops || !d_key_off || !d_out))) {
     set_err(c, std::string(who) + ": null buffer or negative n_keys");
@@ -2514,6 +2567,22 @@ int lc_last_witness_stats(lc_ctx *c, lc_witness_stats *out) {
     s.nodes += d.wit.nodes;
     s.cache_hits += d.wit.cache_hits;
     s.kernel_ms += d.wit.kernel_ms;
+  }
+  *out = s;
+  return 0;
+}
+
+int lc_last_counted_witness_stats(lc_ctx *c, lc_counted_witness_stats *out) {
+  if (!c || !out) return -EINVAL;
+  lc_counted_witness_stats s{};
+  for (const Dev &d : c->devs) {
+    s.n_keys += d.cwit.n_keys;
+    s.n_found += d.cwit.n_found;
+    s.n_budget += d.cwit.n_budget;
+    s.n_unfit += d.cwit.n_unfit;
+    s.nodes += d.cwit.nodes;
+    s.cache_hits += d.cwit.cache_hits;
+    s.kernel_ms += d.cwit.kernel_ms;
   }
   *out = s;
   return 0;
