@@ -569,5 +569,7 @@ const char *lc_build_id(void);
 /* LC_FLAG_SEARCH_WITNESS: lc_last_witness_stats; LC_FLAG_COUNTED_WITNESS:
  * lc_last_counted_witness_stats */
 #include "lincheck_witness.h"
+/* lc_check_events: the per-key split and history completion on the device */
+#include "lincheck_events.h"
 
 #endif /* LINCHECK_H */

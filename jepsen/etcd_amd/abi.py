@@ -138,6 +138,36 @@ class LcAux(ctypes.Structure):
                 ("certificate", ctypes.c_void_p), ("certificate_set", ctypes.c_void_p)]
 
 
+# lc_event / lc_events_out / lc_events_stats (include/lincheck_events.h): events
+# are (n, 6) int32 arrays — key, process, tf, value, expected, version
+LC_EV_SKIP = -1
+LC_EV_INVOKE, LC_EV_OK, LC_EV_FAIL, LC_EV_INFO = 0, 1, 2, 3
+
+
+class LcEvent(ctypes.Structure):
+    _fields_ = [("key", ctypes.c_int32), ("process", ctypes.c_int32), ("tf", ctypes.c_uint32),
+                ("value", ctypes.c_int32), ("expected", ctypes.c_int32),
+                ("version", ctypes.c_int32)]
+
+
+class LcEventsOut(ctypes.Structure):
+    _fields_ = [("ops32", ctypes.c_void_p), ("completion", ctypes.c_void_p),
+                ("key_off", ctypes.c_void_p), ("key_base", ctypes.c_void_p),
+                ("cap", ctypes.c_int64), ("n_ops", ctypes.c_int64)]
+
+
+class LcEventsStats(ctypes.Structure):
+    _fields_ = [("h2d_ms", ctypes.c_double), ("split_ms", ctypes.c_double),
+                ("check_ms", ctypes.c_double), ("total_ms", ctypes.c_double),
+                ("n_events", ctypes.c_int64), ("n_client", ctypes.c_int64),
+                ("n_ops", ctypes.c_int64), ("n_fail_pairs", ctypes.c_int64),
+                ("n_ignored_completions", ctypes.c_int64), ("n_big_keys", ctypes.c_int64)]
+
+
+class LcEventsLimits(ctypes.Structure):
+    _fields_ = [("max_lds_events", ctypes.c_int64), ("lds_process_capacity", ctypes.c_int64)]
+
+
 class LcSynthParams(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("ops_per_key", ctypes.c_int64),
                 ("concurrency", ctypes.c_int32), ("n_values", ctypes.c_int32),
@@ -249,6 +279,18 @@ def lib():
             L.lc_check_frontiers_counted.argtypes = [vp, p, p, i64, p, ctypes.POINTER(LcOpts), p, i32,
                                                      p, p, p, i64]
             L.lc_check_frontiers_counted.restype = ctypes.c_int
+        if hasattr(L, "lc_check_events"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            L.lc_events_pack_host.argtypes = [p, i64, i64, ctypes.POINTER(LcEventsOut)]
+            L.lc_events_pack_host.restype = ctypes.c_int
+            L.lc_events_pack.argtypes = [vp, p, i64, i64, ctypes.POINTER(LcEventsOut)]
+            L.lc_events_pack.restype = ctypes.c_int
+            L.lc_check_events.argtypes = [vp, p, i64, i64, ctypes.POINTER(LcOpts), p,
+                                          ctypes.POINTER(LcAux), ctypes.POINTER(LcEventsOut)]
+            L.lc_check_events.restype = ctypes.c_int
+            L.lc_last_events_stats.argtypes = [vp, ctypes.POINTER(LcEventsStats)]
+            L.lc_last_events_stats.restype = ctypes.c_int
+            L.lc_events_limits.argtypes = [ctypes.POINTER(LcEventsLimits)]
+            L.lc_events_limits.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -336,6 +378,53 @@ class LcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("lincheck error %d: %s" % (code, msg))
         self.code = code
+
+
+def as_events(events):
+    a = np.ascontiguousarray(events, dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 6:
+        a = a.reshape(-1, 6)
+    return a
+
+
+class _EventsOut:
+    """Caller-side arrays of an lc_events_out for `events` over n_keys keys."""
+
+    def __init__(self, events, n_keys):
+        # cap: the invokes among the client events (at least what the library counts)
+        cap = int(((events[:, 0] >= 0) & ((events[:, 2] & 0xFF) == LC_EV_INVOKE)).sum())
+        self.ops32 = np.zeros((cap, 6), dtype=np.int32)
+        self.completion = np.full(cap, -3, dtype=np.int32)
+        self.key_off = np.zeros(max(n_keys, 0) + 1, dtype=np.int64)
+        self.key_base = np.zeros(max(n_keys, 0), dtype=np.int64)
+        self.cap = cap
+        self.c = LcEventsOut(self.ops32.ctypes.data, self.completion.ctypes.data,
+                             self.key_off.ctypes.data, self.key_base.ctypes.data, cap, -1)
+
+    def result(self):
+        n = int(self.c.n_ops)
+        return self.ops32[:n], self.key_off, self.key_base, self.completion[:n]
+
+
+def pack_events_host(events, n_keys):
+    """lc_events_pack_host: the per-key split and history completion of an
+    event array on the host -> (ops32 (n_ops, 6) int32, key_off, key_base,
+    completion: per record the position of its completion event or -1)."""
+    events = as_events(events)
+    out = _EventsOut(events, n_keys)
+    rc = lib().lc_events_pack_host(_ptr(events), len(events), n_keys, ctypes.byref(out.c))
+    if rc != 0:
+        raise LcError(rc, "lc_events_pack_host")
+    return out.result()
+
+
+def events_limits():
+    """lc_events_limits: {"max_lds_events", "lds_process_capacity"}."""
+    s = LcEventsLimits()
+    rc = lib().lc_events_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_events_limits")
+    return {f: getattr(s, f) for f, _ in LcEventsLimits._fields_}
 
 
 class Context:
@@ -480,6 +569,56 @@ class Context:
             raise ValueError(f"key_base has {len(base)} entries for {len(key_off) - 1} keys")
         return self._check_host(lib().lc_check16, ops16, key_off, (_ptr(base),), opts,
                                 raise_on_error, witness, certificate)
+
+    def events_pack(self, events, n_keys):
+        """lc_events_pack: pack_events_host's result, computed on the device."""
+        events = as_events(events)
+        out = _EventsOut(events, n_keys)
+        rc = lib().lc_events_pack(self._h, _ptr(events), len(events), n_keys, ctypes.byref(out.c))
+        if rc != 0:
+            raise LcError(rc, self.last_error())
+        return out.result()
+
+    def check_events(self, events, n_keys, opts=None, raise_on_error=True, witness=False,
+                     certificate=False, packed=False):
+        """lc_check_events: split, completion and check of an event array on
+        the device.  Returns as check() — the per-record outputs indexed like
+        the packed records — and with packed=True one more element, the
+        records as pack_events_host returns them."""
+        events = as_events(events)
+        out = np.zeros(max(n_keys, 0), dtype=RESULT_DTYPE)
+        o = opts if opts is not None else default_opts()
+        pk = _EventsOut(events, n_keys) if packed or witness or certificate else None
+        wit = kind = cert = cset = None
+        aux = None
+        if witness or certificate:
+            wit = np.full(pk.cap, -3, dtype=np.int32)
+            kind = np.full(max(n_keys, 0), -3, dtype=np.int32)
+            if certificate:
+                cert = np.full((max(n_keys, 0), 4), -3, dtype=np.int32)
+                cset = np.zeros(pk.cap, dtype=np.int32)
+            aux = ctypes.byref(LcAux(wit.ctypes.data, kind.ctypes.data,
+                                     cert.ctypes.data if certificate else None,
+                                     cset.ctypes.data if certificate else None))
+        rc = lib().lc_check_events(self._h, _ptr(events), len(events), n_keys, ctypes.byref(o),
+                                   _ptr(out), aux, ctypes.byref(pk.c) if pk else None)
+        if rc != 0 and raise_on_error:
+            raise LcError(rc, self.last_error())
+        n_ops = max(int(pk.c.n_ops), 0) if pk else 0
+        ret = (rc, out)
+        if certificate:
+            ret = (rc, out, wit[:n_ops], kind, cert, cset[:n_ops])
+        elif witness:
+            ret = (rc, out, wit[:n_ops], kind)
+        return ret + (pk.result(),) if packed else ret
+
+    def last_events_stats(self):
+        """lc_last_events_stats: the last events_pack / check_events call."""
+        s = LcEventsStats()
+        rc = lib().lc_last_events_stats(self._h, ctypes.byref(s))
+        if rc != 0:
+            raise LcError(rc, "lc_last_events_stats")
+        return {f: getattr(s, f) for f, _ in LcEventsStats._fields_}
 
     def check_frontiers(self, ops, key_off, stop_ops, max_per_key=10, opts=None):
         """lc_check_frontiers (include/lincheck_fx.h, ABI 4): for every key,

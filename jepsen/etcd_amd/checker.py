@@ -38,7 +38,10 @@ arguments raise LcError, and jepsen's check-safe turns an exception into
 """
 import os
 
-from . import abi, diagnostics as D, history as H, linear_svg as LS, timeline as TL, witness as W
+import numpy as np
+
+from . import abi, diagnostics as D, events as E, history as H, linear_svg as LS, timeline as TL, \
+    witness as W
 
 UNKNOWN = "unknown"
 # an invalid key the batched device search (lc_check_frontiers) could not
@@ -105,8 +108,17 @@ class RegisterChecker:
 
     def __init__(self, model=None, device_mask=0, max_configs_per_key=0, independent=True,
                  timeline_dir=None, time_budget_ms=0, whole_gpu=True, frontier_max_keys=1000,
-                 counted_classes=True, search_witness=False, counted_witness=True):
+                 counted_classes=True, search_witness=False, counted_witness=True,
+                 device_split=False):
         self.model = model or VersionedRegister(0, None)
+        # the per-key split and the history completion on the device
+        # (lc_check_events): check() writes one event record per op map
+        # (events.encode) and rebuilds the completed ops from the records the
+        # device packed.  A history events cannot express (events.Unsupported)
+        # takes the host path; split_fallbacks counts those calls.  Value ids
+        # are then the whole history's, not per key
+        self.device_split = device_split
+        self.split_fallbacks = 0
         # cap on the frontier re-searches one check() runs for diagnostics of
         # witnessed invalid keys (each is one key's search up to its failing
         # return, bounded by max_configs_per_key / time_budget_ms); 0: none
@@ -167,24 +179,79 @@ class RegisterChecker:
             self._fx = FrontierExchange(device=dev)
         return self._fx
 
+    def _check_split_on_device(self, history, o):
+        """The front half of check() through lc_check_events: what H.pack and
+        the check16 / check32 call return, rebuilt from the device's records.
+        None when the history cannot be written as events."""
+        m = self.model
+        try:
+            ev, keys, table, index = E.encode(history, m.name, self.independent, m.value)
+        except E.Unsupported:
+            self.split_fallbacks += 1
+            return None
+        if not keys:
+            return [], None, None, None, None, None
+        _, res, wit, kind, cert, cset, (ops32, key_off, key_base, completion) = \
+            self._context().check_events(ev, len(keys), o, witness=True, certificate=True, packed=True)
+        # positions -> the history's own indices
+        base = np.repeat(key_base, np.diff(key_off))
+        call = ops32[:, 4].astype(np.uint32).astype(np.int64) + base
+        ret32 = ops32[:, 5].astype(np.uint32).astype(np.int64)
+        crashed = ret32 == abi.LC_INF32
+        ret = np.where(crashed, 0, ret32 + base)
+        ops = np.zeros((len(ops32), 6), dtype=np.int64)
+        ops[:, :4] = ops32[:, :4]
+        ops[:, 4] = index[call]
+        ops[:, 5] = np.where(crashed, abi.LC_INF, index[ret])
+        res = res.copy()
+        failed = res["fail_prefix_end"] >= 0
+        res["fail_prefix_end"][failed] = index[res["fail_prefix_end"][failed]]
+
+        def op_at(pos):  # the op map as split_by_key hands it on
+            op = dict(history[pos])
+            op.setdefault("index", int(index[pos]))
+            if self.independent:
+                op["value"] = op["value"].value
+            return op
+
+        done = []
+        for i in range(len(keys)):
+            d = []
+            for r in range(int(key_off[i]), int(key_off[i + 1])):
+                inv = op_at(int(call[r]))
+                comp = op_at(int(completion[r])) if completion[r] >= 0 else None
+                ok = not crashed[r]
+                d.append({"f": H._kw(inv.get("f")), "value": comp.get("value") if ok else inv.get("value"),
+                          "call": int(ops[r, 4]), "ret": int(ops[r, 5]), "invoke": inv,
+                          "completion": comp, "type": "ok" if ok else "info"})
+            done.append(d)
+        return keys, ops, key_off, done, [table] * len(keys), (res, wit, kind, cert, cset)
+
     def check(self, test, history, opts=None):
         m = self.model
-        values = []
-        keys, ops, key_off, done = H.pack(history, model=m.name, independent=self.independent,
-                                          init_value=m.value, values_out=values)
-        if not keys:
-            return {"valid?": True, "results": {}, "failures": []}
         # the initial value is interned first in every key (id 0); the mutex
         # starts free (id MUTEX_FREE)
         init = H.MUTEX_FREE if m.name == "mutex" else (0 if m.value is not None else H.LC_NIL)
         o = abi.default_opts(self.max_configs_per_key, m.version, init, flags=self._flags(),
                              time_budget_ms=self.time_budget_ms)
+        split = self._check_split_on_device(history, o) if self.device_split else None
+        if split is not None:
+            keys, ops, key_off, done, values, checked = split
+        else:
+            checked = None
+            values = []
+            keys, ops, key_off, done = H.pack(history, model=m.name, independent=self.independent,
+                                              init_value=m.value, values_out=values)
+        if not keys:
+            return {"valid?": True, "results": {}, "failures": []}
         # the drop-in's call (ABI 5): 16-byte records when every value id
         # fits 15 bits, else 24-byte ones — what crosses PCIe (the JVM shim
         # packs them directly; here lc_pack16 / lc_pack32 narrow the 48-byte
         # pack by the same rules)
-        p16 = abi.pack16(ops, key_off)
-        if p16 is not None:
+        p16 = abi.pack16(ops, key_off) if checked is None else None
+        if checked is not None:
+            res, wit, kind, cert, cset = checked
+        elif p16 is not None:
             ops16, key_base = p16
             _, res, wit, kind, cert, cset = self._context().check16(
                 ops16, key_off, key_base, o, witness=True, certificate=True)

@@ -33,6 +33,7 @@
 #include "../../../include/lincheck_fx.h"
 #include "kernels.h"
 #include "counted.h"
+#include "events.h"
 
 #ifndef LC_BUILD_ID
 #define LC_BUILD_ID "unknown"
@@ -210,6 +211,23 @@ struct Dev {
   lc_totals tot{};
 };
 
+// lc_check_events / lc_events_pack: the event path's own workspace on the
+// context's first device (grown on demand, freed at lc_close) and the last
+// call's statistics.
+struct EvState {
+  Buf<lc_event> d_ev;
+  Buf<int32_t> d_cnt, d_cursor, d_match, d_nops, d_nfail, d_nign, d_completion;
+  Buf<int64_t> d_seg_off, d_key_off, d_key_base;
+  Buf<uint32_t> d_seg;
+  Buf<unsigned long long> d_gtab;
+  Buf<lc_op32> d_ops32;
+  Buf<lc_key_result> d_res;
+  Buf<lcev::Status> d_status;
+  lcev::Status *h_status = nullptr;  // pinned
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  lc_events_stats stats{};
+};
+
 }  // namespace
 
 struct lc_ctx {
@@ -226,6 +244,7 @@ struct lc_ctx {
   std::vector<std::pair<const char *, uint64_t>> pinned;
   std::mutex pin_mu;
   lc_call_profile prof{};  // lc_last_call_profile
+  EvState evs;             // lc_check_events
 };
 
 namespace {
@@ -2407,6 +2426,177 @@ int frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64
   return 0;
 }
 
+// lc_events_pack / lc_check_events: the events copied to the context's first
+// device and split, completed and packed there (events.hip).  On return the
+// stream has drained, s.h_status holds the call's counts, and the records
+// are in s.d_ops32 / d_completion / d_key_off / d_key_base.
+int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_events, int64_t n_keys) {
+  const std::string name(who);
+  EvState &s = c->evs;
+  s.stats = lc_events_stats{};
+  if (n_events < 0 || n_keys < 0 || (n_events > 0 && !ev)) {
+    set_err(c, name + ": null events or a negative count");
+    return -EINVAL;
+  }
+  if (n_events >= (int64_t(1) << 31) || n_keys >= (int64_t(1) << 31)) {
+    set_err(c, name + ": 2^31 or more events or keys");
+    return -EINVAL;
+  }
+  Dev &d = c->devs[0];
+  HIP_TRY(c, hipSetDevice(d.id));
+  (void)settle_status(d);
+  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
+  hipStream_t st = d.stream;
+  if (!s.e0) {
+    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2}) HIP_TRY(c, hipEventCreate(e));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_status), sizeof(lcev::Status), 0));
+  }
+  const size_t n = (size_t)n_events, k = (size_t)n_keys;
+  int e = ensure(c, s.d_ev, sizeof(lc_event) * n);
+  if (!e) e = ensure(c, s.d_cnt, sizeof(int32_t) * k);
+  if (!e) e = ensure(c, s.d_cursor, sizeof(int32_t) * k);
+  if (!e) e = ensure(c, s.d_seg_off, sizeof(int64_t) * (k + 1));
+  if (!e) e = ensure(c, s.d_seg, sizeof(uint32_t) * n);
+  if (!e) e = ensure(c, s.d_match, sizeof(int32_t) * n);
+  if (!e) e = ensure(c, s.d_gtab, 2 * sizeof(unsigned long long) * n);
+  if (!e) e = ensure(c, s.d_nops, sizeof(int32_t) * k);
+  if (!e) e = ensure(c, s.d_nfail, sizeof(int32_t) * k);
+  if (!e) e = ensure(c, s.d_nign, sizeof(int32_t) * k);
+  if (!e) e = ensure(c, s.d_key_off, sizeof(int64_t) * (k + 1));
+  if (!e) e = ensure(c, s.d_key_base, sizeof(int64_t) * k);
+  if (!e) e = ensure(c, s.d_ops32, sizeof(lc_op32) * n);
+  if (!e) e = ensure(c, s.d_completion, sizeof(int32_t) * n);
+  if (!e) e = ensure(c, s.d_status, sizeof(lcev::Status));
+  if (e) return e;
+  HIP_TRY(c, hipEventRecord(s.e0, st));
+  if (n) HIP_TRY(c, hipMemcpyAsync(s.d_ev.p, ev, sizeof(lc_event) * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipEventRecord(s.e1, st));
+  // no counter of an earlier call, larger or smaller, survives
+  HIP_TRY(c, hipMemsetAsync(s.d_status.p, 0, sizeof(lcev::Status), st));
+  if (k > 1) {
+    HIP_TRY(c, hipMemsetAsync(s.d_cnt.p, 0, sizeof(int32_t) * k, st));
+    HIP_TRY(c, hipMemsetAsync(s.d_cursor.p, 0, sizeof(int32_t) * k, st));
+  }
+  lcev::Ws w{};
+  w.ev = s.d_ev.p;
+  w.n = n_events;
+  w.k = n_keys;
+  w.cnt = s.d_cnt.p;
+  w.cursor = s.d_cursor.p;
+  w.seg_off = s.d_seg_off.p;
+  w.seg = s.d_seg.p;
+  w.match = s.d_match.p;
+  w.gtab = s.d_gtab.p;
+  w.nops = s.d_nops.p;
+  w.nfail = s.d_nfail.p;
+  w.nign = s.d_nign.p;
+  w.key_off = s.d_key_off.p;
+  w.key_base = s.d_key_base.p;
+  w.ops32 = s.d_ops32.p;
+  w.completion = s.d_completion.p;
+  w.status = s.d_status.p;
+  HIP_TRY(c, lcev::launch_events(w, st));
+  HIP_TRY(c, hipEventRecord(s.e2, st));
+  HIP_TRY(c, hipMemcpyAsync(s.h_status, s.d_status.p, sizeof(lcev::Status), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) s.stats.h2d_ms = ms;
+  if (hipEventElapsedTime(&ms, s.e1, s.e2) == hipSuccess) s.stats.split_ms = ms;
+  const lcev::Status &h = *s.h_status;
+  s.stats.n_events = n_events;
+  s.stats.n_client = h.n_client;
+  s.stats.n_ops = h.n_ops;
+  s.stats.n_fail_pairs = h.n_fail;
+  s.stats.n_ignored_completions = h.n_ignored;
+  s.stats.n_big_keys = h.n_big;
+  if (h.err) {
+    set_err(c, name + ": an event with a key outside [-1, n_keys) or a type above 3 (the last one at position " +
+                   std::to_string(h.err_pos) + ")");
+    return -EINVAL;
+  }
+  return 0;
+}
+
+// The packed records of the last events_device call into the caller's arrays.
+int events_copy_out(lc_ctx *c, const char *who, int64_t n_keys, lc_events_out *out) {
+  EvState &s = c->evs;
+  const lcev::Status &h = *s.h_status;
+  if (!out->key_off || (n_keys > 0 && !out->key_base) || out->cap < h.n_invoke ||
+      (h.n_ops > 0 && (!out->ops32 || !out->completion))) {
+    set_err(c, std::string(who) + ": lc_events_out: a null array, or cap below the number of invokes");
+    return -EINVAL;
+  }
+  hipStream_t st = c->devs[0].stream;
+  const size_t k = (size_t)n_keys, m = (size_t)h.n_ops;
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(out->ops32, s.d_ops32.p, sizeof(lc_op32) * m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(out->completion, s.d_completion.p, sizeof(int32_t) * m,
+                              hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(out->key_off, s.d_key_off.p, sizeof(int64_t) * (k + 1), hipMemcpyDeviceToHost,
+                            st));
+  if (k)
+    HIP_TRY(c, hipMemcpyAsync(out->key_base, s.d_key_base.p, sizeof(int64_t) * k, hipMemcpyDeviceToHost,
+                              st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  out->n_ops = h.n_ops;
+  return 0;
+}
+
+// lc_check_events after events_device: the records, resident, through
+// lc_check_device32's path; results and lc_aux outputs copied to the host.
+int events_check(lc_ctx *c, int64_t n_keys, const lc_opts *opts, lc_key_result *out, const lc_aux *aux) {
+  EvState &s = c->evs;
+  Dev &d = c->devs[0];
+  if (n_keys == 0) return 0;
+  if (!out) {
+    set_err(c, "lc_check_events: null out");
+    return -EINVAL;
+  }
+  const size_t k = (size_t)n_keys, m = (size_t)s.h_status->n_ops;
+  const bool want_wit = aux && aux->witness && aux->witness_kind;
+  const bool want_cert = aux && aux->certificate;
+  if (aux && (aux->witness || aux->certificate) && !(aux->witness && aux->witness_kind)) {
+    set_err(c, "lc_check_events: lc_aux needs witness and witness_kind");
+    return -EINVAL;
+  }
+  int e = ensure(c, s.d_res, sizeof(lc_key_result) * k);
+  if (!e && want_wit) e = ensure(c, d.d_wit, sizeof(int32_t) * m);
+  if (!e && want_wit) e = ensure(c, d.d_kind, sizeof(int32_t) * k);
+  if (!e && want_cert) e = ensure(c, d.d_cert, 4 * sizeof(int32_t) * k);
+  if (!e && want_cert) e = ensure(c, d.d_cset, sizeof(int32_t) * m);
+  if (e) return e;
+  lc_aux dev_aux{};
+  if (want_wit) {
+    dev_aux.witness = d.d_wit.p;
+    dev_aux.witness_kind = d.d_kind.p;
+  }
+  if (want_cert) {
+    dev_aux.certificate = d.d_cert.p;
+    dev_aux.certificate_set = d.d_cset.p;
+  }
+  e = check_device(c, "lc_check_events", s.d_ops32.p, true, s.d_key_off.p, s.d_key_base.p, n_keys, opts,
+                   s.d_res.p, nullptr, want_wit ? &dev_aux : nullptr);
+  if (e) return e;
+  hipStream_t st = d.stream;
+  HIP_TRY(c, hipMemcpyAsync(out, s.d_res.p, sizeof(lc_key_result) * k, hipMemcpyDeviceToHost, st));
+  if (want_wit) {
+    if (m)
+      HIP_TRY(c, hipMemcpyAsync(aux->witness, d.d_wit.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(aux->witness_kind, d.d_kind.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost,
+                              st));
+  }
+  if (want_cert) {
+    HIP_TRY(c, hipMemcpyAsync(aux->certificate, d.d_cert.p, 4 * sizeof(int32_t) * k,
+                              hipMemcpyDeviceToHost, st));
+    if (m && aux->certificate_set)
+      HIP_TRY(c, hipMemcpyAsync(aux->certificate_set, d.d_cset.p, sizeof(int32_t) * m,
+                                hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2479,6 +2669,20 @@ int lc_open(uint32_t device_mask, lc_ctx **out) {
 
 void lc_close(lc_ctx *c) {
   if (!c) return;
+  if (!c->devs.empty()) {
+    EvState &s = c->evs;
+    (void)hipSetDevice(c->devs[0].id);
+    if (c->devs[0].stream) (void)hipStreamSynchronize(c->devs[0].stream);
+    // every Buf of EvState
+    for (void *b : std::initializer_list<void *>{
+             s.d_ev.p, s.d_cnt.p, s.d_cursor.p, s.d_match.p, s.d_nops.p, s.d_nfail.p, s.d_nign.p,
+             s.d_completion.p, s.d_seg_off.p, s.d_key_off.p, s.d_key_base.p, s.d_seg.p, s.d_gtab.p,
+             s.d_ops32.p, s.d_res.p, s.d_status.p})
+      if (b) (void)hipFree(b);
+    if (s.h_status) (void)hipHostFree(s.h_status);
+    for (hipEvent_t e : {s.e0, s.e1, s.e2})
+      if (e) (void)hipEventDestroy(e);
+  }
   for (auto &f : c->fxs) lc_fx_close(f.first);
   if (c->fx_all) lc_fx_close(c->fx_all);
   for (auto &pr : c->pinned) (void)hipHostUnregister(const_cast<char *>(pr.first));
@@ -2864,6 +3068,42 @@ int lc_check_frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_o
     set_err(c, "lc_check_frontiers_counted: out of host memory");
     return -ENOMEM;
   }
+}
+
+int lc_events_pack(lc_ctx *c, const lc_event *ev, int64_t n_events, int64_t n_keys, lc_events_out *out) {
+  if (!c) return -EINVAL;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!out) {
+    set_err(c, "lc_events_pack: null out");
+    return -EINVAL;
+  }
+  int rc = events_device(c, "lc_events_pack", ev, n_events, n_keys);
+  if (!rc) rc = events_copy_out(c, "lc_events_pack", n_keys, out);
+  c->evs.stats.total_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+int lc_check_events(lc_ctx *c, const lc_event *ev, int64_t n_events, int64_t n_keys, const lc_opts *opts,
+                    lc_key_result *out, const lc_aux *aux, lc_events_out *packed) {
+  if (!c) return -EINVAL;
+  const auto t0 = std::chrono::steady_clock::now();
+  auto ms = [&] {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  int rc = events_device(c, "lc_check_events", ev, n_events, n_keys);
+  if (!rc && packed) rc = events_copy_out(c, "lc_check_events", n_keys, packed);
+  const double t1 = ms();
+  if (!rc) rc = events_check(c, n_keys, opts, out, aux);
+  c->evs.stats.check_ms = ms() - t1;
+  c->evs.stats.total_ms = ms();
+  return rc;
+}
+
+int lc_last_events_stats(lc_ctx *c, lc_events_stats *out) {
+  if (!c || !out) return -EINVAL;
+  *out = c->evs.stats;
+  return 0;
 }
 
 int lc_pack32(const lc_op *ops, const int64_t *key_off, int64_t n_keys, lc_op32 *out,
