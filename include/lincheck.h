@@ -571,5 +571,7 @@ const char *lc_build_id(void);
 #include "lincheck_witness.h"
 /* lc_check_events: the per-key split and history completion on the device */
 #include "lincheck_events.h"
+/* lc_set_full: jepsen's set-full checker on the device */
+#include "lincheck_setfull.h"
 
 #endif /* LINCHECK_H */

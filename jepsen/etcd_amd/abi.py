@@ -168,6 +168,34 @@ class LcEventsLimits(ctypes.Structure):
     _fields_ = [("max_lds_events", ctypes.c_int64), ("lds_process_capacity", ctypes.c_int64)]
 
 
+# lc_set_full (include/lincheck_setfull.h): adds, reads and elements are numpy
+# structured arrays of the C structs' layout
+LC_SF_NEVER_READ, LC_SF_STABLE, LC_SF_LOST = 0, 1, 2
+LC_SF_STALE, LC_SF_DUPLICATED = 1, 2
+SF_ADD_DTYPE = np.dtype([("value", "<i8"), ("ok_time", "<i8"), ("inv_pos", "<i4"), ("ok_pos", "<i4")])
+SF_READ_DTYPE = np.dtype([("inv_time", "<i8"), ("ok_time", "<i8"), ("off", "<i8"), ("inv_pos", "<i4"),
+                          ("ok_pos", "<i4"), ("len", "<i4"), ("pad", "<i4")])
+SF_ELEMENT_DTYPE = np.dtype([("outcome", "<i4"), ("flags", "<i4"), ("known_pos", "<i4"),
+                             ("last_present", "<i4"), ("last_absent", "<i4"), ("dup_max", "<i4"),
+                             ("stable_latency_ms", "<i8"), ("lost_latency_ms", "<i8")])
+assert (SF_ADD_DTYPE.itemsize, SF_READ_DTYPE.itemsize, SF_ELEMENT_DTYPE.itemsize) == (24, 40, 40)
+
+
+class LcSfSummary(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int32), ("linearizable", ctypes.c_int32),
+                ("n_elements", ctypes.c_int64), ("n_stable", ctypes.c_int64),
+                ("n_lost", ctypes.c_int64), ("n_never_read", ctypes.c_int64),
+                ("n_stale", ctypes.c_int64), ("n_duplicated", ctypes.c_int64),
+                ("n_phantom", ctypes.c_int64), ("n_tiles", ctypes.c_int64),
+                ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
+
+
+class LcSfLimits(ctypes.Structure):
+    _fields_ = [("tile_bytes", ctypes.c_int64), ("default_tile_bytes", ctypes.c_int64),
+                ("max_position", ctypes.c_int64), ("value_bytes", ctypes.c_int64)]
+
+
 class LcSynthParams(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("ops_per_key", ctypes.c_int64),
                 ("concurrency", ctypes.c_int32), ("n_values", ctypes.c_int32),
@@ -291,6 +319,13 @@ def lib():
             L.lc_last_events_stats.restype = ctypes.c_int
             L.lc_events_limits.argtypes = [ctypes.POINTER(LcEventsLimits)]
             L.lc_events_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_set_full"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            L.lc_set_full_host.argtypes = [p, i64, p, i64, p, i64, i32, p, ctypes.POINTER(LcSfSummary)]
+            L.lc_set_full_host.restype = ctypes.c_int
+            L.lc_set_full.argtypes = [vp, p, i64, p, i64, p, i64, i32, p, ctypes.POINTER(LcSfSummary)]
+            L.lc_set_full.restype = ctypes.c_int
+            L.lc_set_full_limits.argtypes = [ctypes.POINTER(LcSfLimits)]
+            L.lc_set_full_limits.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -425,6 +460,37 @@ def events_limits():
     if rc != 0:
         raise LcError(rc, "lc_events_limits")
     return {f: getattr(s, f) for f, _ in LcEventsLimits._fields_}
+
+
+def _set_full_args(adds, reads, read_values):
+    adds = np.ascontiguousarray(adds, dtype=SF_ADD_DTYPE)
+    reads = np.ascontiguousarray(reads, dtype=SF_READ_DTYPE)
+    read_values = np.ascontiguousarray(read_values, dtype=np.int64)
+    return adds, reads, read_values, np.zeros(len(adds), dtype=SF_ELEMENT_DTYPE), LcSfSummary()
+
+
+def _set_full_summary(s):
+    return {f: getattr(s, f) for f, _ in LcSfSummary._fields_}
+
+
+def set_full_host(adds, reads, read_values, linearizable=True):
+    """lc_set_full_host: set-full's rules on the host -> (elements
+    (SF_ELEMENT_DTYPE, one per add), the summary as a dict)."""
+    adds, reads, read_values, out, s = _set_full_args(adds, reads, read_values)
+    rc = lib().lc_set_full_host(_ptr(adds), len(adds), _ptr(reads), len(reads), _ptr(read_values),
+                                len(read_values), int(bool(linearizable)), _ptr(out), ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_set_full_host")
+    return out, _set_full_summary(s)
+
+
+def set_full_limits():
+    """lc_set_full_limits: {"tile_bytes", "default_tile_bytes", "max_position", "value_bytes"}."""
+    s = LcSfLimits()
+    rc = lib().lc_set_full_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_set_full_limits")
+    return {f: getattr(s, f) for f, _ in LcSfLimits._fields_}
 
 
 class Context:
@@ -611,6 +677,16 @@ class Context:
         elif witness:
             ret = (rc, out, wit[:n_ops], kind)
         return ret + (pk.result(),) if packed else ret
+
+    def set_full(self, adds, reads, read_values, linearizable=True):
+        """lc_set_full: set_full_host's result, computed on the device."""
+        adds, reads, read_values, out, s = _set_full_args(adds, reads, read_values)
+        rc = lib().lc_set_full(self._h, _ptr(adds), len(adds), _ptr(reads), len(reads),
+                               _ptr(read_values), len(read_values), int(bool(linearizable)),
+                               _ptr(out), ctypes.byref(s))
+        if rc != 0:
+            raise LcError(rc, self.last_error() if rc == -22 else "lc_set_full")
+        return out, _set_full_summary(s)
 
     def last_events_stats(self):
         """lc_last_events_stats: the last events_pack / check_events call."""

@@ -34,6 +34,7 @@
 #include "kernels.h"
 #include "counted.h"
 #include "events.h"
+#include "setfull.h"
 
 #ifndef LC_BUILD_ID
 #define LC_BUILD_ID "unknown"
@@ -228,6 +229,21 @@ struct EvState {
   lc_events_stats stats{};
 };
 
+// lc_set_full: its workspace on the context's first device (grown on demand,
+// freed at lc_close).
+struct SfState {
+  Buf<lc_sf_add> d_adds;
+  Buf<lc_sf_read> d_reads;
+  Buf<int64_t> d_values, d_work_off, d_tab_key, d_counters;
+  Buf<lcsf::Ent> d_tab_ent;
+  Buf<int32_t> d_r_inv, d_r_ok, d_status;
+  Buf<uint32_t> d_bitmap;
+  Buf<uint8_t> d_dup;
+  Buf<lc_sf_element> d_out;
+  int64_t *h_small = nullptr;  // pinned: the status words, then the counters
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+};
+
 }  // namespace
 
 struct lc_ctx {
@@ -245,6 +261,7 @@ struct lc_ctx {
   std::mutex pin_mu;
   lc_call_profile prof{};  // lc_last_call_profile
   EvState evs;             // lc_check_events
+  SfState sfs;             // lc_set_full
 };
 
 namespace {
@@ -2426,6 +2443,135 @@ int frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64
   return 0;
 }
 
+// lc_set_full: the arrays copied to the context's first device, the element
+// table built, then one mark pass and one element pass per tile (setfull.hip).
+// The duplicates' multiplicities, where the device saw any, the summary and
+// the verdict are the host's (setfull_host.cpp).
+int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_read *reads, int64_t n_reads,
+                    const int64_t *read_values, int64_t n_values, int32_t linearizable, lc_sf_element *out,
+                    lc_sf_summary *sum) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const char *why = nullptr;
+  if (lcsf::check_contract(adds, n_adds, reads, n_reads, read_values, n_values, &why)) {
+    set_err(c, std::string("lc_set_full: ") + why);
+    return -EINVAL;
+  }
+  if (n_adds > 0 && !out) {
+    set_err(c, "lc_set_full: null out");
+    return -EINVAL;
+  }
+  if (n_adds == 0 || n_reads == 0) {  // nothing for the device to do
+    const int rc = lc_set_full_host(adds, n_adds, reads, n_reads, read_values, n_values, linearizable, out, sum);
+    if (rc == -EINVAL) set_err(c, "lc_set_full: two adds of one value");
+    return rc;
+  }
+  SfState &s = c->sfs;
+  Dev &d = c->devs[0];
+  HIP_TRY(c, hipSetDevice(d.id));
+  (void)settle_status(d);
+  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
+  hipStream_t st = d.stream;
+  constexpr size_t kSmall = 4 + lcsf::kCounterShards * lcsf::kCounterStride;  // in int64
+  if (!s.e0) {
+    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2}) HIP_TRY(c, hipEventCreate(e));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
+  }
+  lc_sf_limit_info lim;
+  lc_set_full_limits(&lim);
+  const size_t ne = (size_t)n_adds, nr = (size_t)n_reads;
+  const int64_t wpr = (n_reads + 31) / 32;
+  int64_t tile_rows = lim.tile_bytes / (wpr * 4);  // a tile holds at least one row
+  tile_rows = std::max<int64_t>(1, std::min(tile_rows, n_adds));
+  const int64_t n_tiles = (n_adds + tile_rows - 1) / tile_rows;
+  const uint64_t cap = lcsf::table_capacity(n_adds);
+  std::vector<int64_t> work_off(nr + 1);
+  work_off[0] = 0;
+  for (size_t r = 0; r < nr; r++) work_off[r + 1] = work_off[r] + reads[r].len;
+  int e = ensure(c, s.d_adds, sizeof(lc_sf_add) * ne);
+  if (!e) e = ensure(c, s.d_reads, sizeof(lc_sf_read) * nr);
+  if (!e) e = ensure(c, s.d_values, sizeof(int64_t) * (size_t)n_values);
+  if (!e) e = ensure(c, s.d_work_off, sizeof(int64_t) * (nr + 1));
+  if (!e) e = ensure(c, s.d_tab_key, sizeof(int64_t) * cap);
+  if (!e) e = ensure(c, s.d_tab_ent, sizeof(lcsf::Ent) * cap);
+  if (!e) e = ensure(c, s.d_r_inv, sizeof(int32_t) * nr);
+  if (!e) e = ensure(c, s.d_r_ok, sizeof(int32_t) * nr);
+  if (!e) e = ensure(c, s.d_bitmap, sizeof(uint32_t) * (size_t)(tile_rows * wpr));
+  if (!e) e = ensure(c, s.d_dup, ne);
+  if (!e) e = ensure(c, s.d_counters, sizeof(int64_t) * lcsf::kCounterShards * lcsf::kCounterStride);
+  if (!e) e = ensure(c, s.d_status, sizeof(int32_t) * 4);
+  if (!e) e = ensure(c, s.d_out, sizeof(lc_sf_element) * ne);
+  if (e) return e;
+  HIP_TRY(c, hipEventRecord(s.e0, st));
+  HIP_TRY(c, hipMemcpyAsync(s.d_adds.p, adds, sizeof(lc_sf_add) * ne, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(s.d_reads.p, reads, sizeof(lc_sf_read) * nr, hipMemcpyHostToDevice, st));
+  if (n_values)
+    HIP_TRY(c, hipMemcpyAsync(s.d_values.p, read_values, sizeof(int64_t) * (size_t)n_values,
+                              hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(s.d_work_off.p, work_off.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice,
+                            st));
+  HIP_TRY(c, hipEventRecord(s.e1, st));
+  // no counter or mark of an earlier call survives
+  HIP_TRY(c, hipMemsetAsync(s.d_counters.p, 0, sizeof(int64_t) * lcsf::kCounterShards * lcsf::kCounterStride, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_status.p, 0, sizeof(int32_t) * 4, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_dup.p, 0, ne, st));
+  lcsf::Ws w{};
+  w.adds = s.d_adds.p;
+  w.reads = s.d_reads.p;
+  w.values = s.d_values.p;
+  w.work_off = s.d_work_off.p;
+  w.n_adds = n_adds;
+  w.n_reads = n_reads;
+  w.n_work = work_off[nr];
+  w.tab_key = s.d_tab_key.p;
+  w.tab_ent = s.d_tab_ent.p;
+  w.cap = cap;
+  w.r_inv = s.d_r_inv.p;
+  w.r_ok = s.d_r_ok.p;
+  w.bitmap = s.d_bitmap.p;
+  w.wpr = wpr;
+  w.dup_seen = s.d_dup.p;
+  w.counters = s.d_counters.p;
+  w.status = s.d_status.p;
+  w.out = s.d_out.p;
+  HIP_TRY(c, lcsf::launch_table(w, st));
+  for (int64_t e0 = 0; e0 < n_adds; e0 += tile_rows)
+    HIP_TRY(c, lcsf::launch_tile(w, e0, std::min(e0 + tile_rows, n_adds), st));
+  HIP_TRY(c, hipEventRecord(s.e2, st));
+  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
+  int64_t *h_counters = s.h_small + 4;
+  HIP_TRY(c, hipMemcpyAsync(h_status, s.d_status.p, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h_counters, s.d_counters.p,
+                            sizeof(int64_t) * lcsf::kCounterShards * lcsf::kCounterStride, hipMemcpyDeviceToHost,
+                            st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (h_status[0]) {
+    set_err(c, "lc_set_full: two adds of one value (element " + std::to_string(h_status[1]) + " is one)");
+    return -EINVAL;
+  }
+  HIP_TRY(c, hipMemcpyAsync(out, s.d_out.p, sizeof(lc_sf_element) * ne, hipMemcpyDeviceToHost, st));
+  std::vector<uint8_t> marked;
+  if (h_status[2]) {
+    marked.resize(ne);
+    HIP_TRY(c, hipMemcpyAsync(marked.data(), s.d_dup.p, ne, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  // duplicates, exact but not fast: the multiplicities of the marked elements
+  // in one pass over the payload (a history without duplicates never takes it)
+  if (h_status[2])
+    if (int rc = lcsf::count_duplicates(adds, n_adds, reads, n_reads, read_values, marked.data(), out)) return rc;
+  if (sum) {
+    lcsf::summarize(out, n_adds, linearizable, sum);
+    sum->n_phantom = 0;
+    for (int i = 0; i < lcsf::kCounterShards; i++) sum->n_phantom += h_counters[i * lcsf::kCounterStride];
+    sum->n_tiles = n_tiles;
+    float ms = 0;
+    sum->h2d_ms = hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess ? ms : 0;
+    sum->kernel_ms = hipEventElapsedTime(&ms, s.e1, s.e2) == hipSuccess ? ms : 0;
+    sum->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return 0;
+}
+
 // lc_events_pack / lc_check_events: the events copied to the context's first
 // device and split, completed and packed there (events.hip).  On return the
 // stream has drained, s.h_status holds the call's counts, and the records
@@ -2681,6 +2827,15 @@ void lc_close(lc_ctx *c) {
       if (b) (void)hipFree(b);
     if (s.h_status) (void)hipHostFree(s.h_status);
     for (hipEvent_t e : {s.e0, s.e1, s.e2})
+      if (e) (void)hipEventDestroy(e);
+    // every Buf of SfState
+    SfState &f = c->sfs;
+    for (void *b : std::initializer_list<void *>{
+             f.d_adds.p, f.d_reads.p, f.d_values.p, f.d_work_off.p, f.d_tab_key.p, f.d_counters.p,
+             f.d_tab_ent.p, f.d_r_inv.p, f.d_r_ok.p, f.d_status.p, f.d_bitmap.p, f.d_dup.p, f.d_out.p})
+      if (b) (void)hipFree(b);
+    if (f.h_small) (void)hipHostFree(f.h_small);
+    for (hipEvent_t e : {f.e0, f.e1, f.e2})
       if (e) (void)hipEventDestroy(e);
   }
   for (auto &f : c->fxs) lc_fx_close(f.first);
@@ -3098,6 +3253,18 @@ int lc_check_events(lc_ctx *c, const lc_event *ev, int64_t n_events, int64_t n_k
   c->evs.stats.check_ms = ms() - t1;
   c->evs.stats.total_ms = ms();
   return rc;
+}
+
+int lc_set_full(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_read *reads, int64_t n_reads,
+                const int64_t *read_values, int64_t n_values, int32_t linearizable, lc_sf_element *out,
+                lc_sf_summary *sum) {
+  if (!c) return -EINVAL;
+  try {
+    return set_full_device(c, adds, n_adds, reads, n_reads, read_values, n_values, linearizable, out, sum);
+  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
+    set_err(c, "lc_set_full: out of host memory");
+    return -ENOMEM;
+  }
 }
 
 int lc_last_events_stats(lc_ctx *c, lc_events_stats *out) {
