@@ -573,5 +573,7 @@ const char *lc_build_id(void);
 #include "lincheck_events.h"
 /* lc_set_full: jepsen's set-full checker on the device */
 #include "lincheck_setfull.h"
+/* lc_append_check: Elle's list-append checker with the graph on the device */
+#include "lincheck_append.h"
 
 #endif /* LINCHECK_H */

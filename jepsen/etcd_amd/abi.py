@@ -196,6 +196,53 @@ class LcSfLimits(ctypes.Structure):
                 ("max_position", ctypes.c_int64), ("value_bytes", ctypes.c_int64)]
 
 
+# lc_append_check (include/lincheck_append.h): txns, mops, edges, keys and
+# witness steps are numpy structured arrays of the C structs' layout
+LC_AP_OK, LC_AP_INFO, LC_AP_FAIL = 0, 1, 2
+LC_AP_APPEND, LC_AP_READ = 0, 1
+LC_AP_WW, LC_AP_WR, LC_AP_RW, LC_AP_RT = 0, 1, 2, 3
+LC_AP_MAX_CYCLES = 16
+LC_AP_R_NONPREFIX, LC_AP_R_DUPLICATE, LC_AP_R_G1A, LC_AP_R_PHANTOM, LC_AP_R_G1B, LC_AP_R_INTERNAL, \
+    LC_AP_R_EXTERNAL = 1, 2, 4, 8, 16, 32, 64
+LC_AP_R_ANOMALY = 63
+LC_AP_K_INCOMPATIBLE, LC_AP_K_NO_ORDER = 1, 2
+LC_AP_CLASSES = ("G0", "G1c", "G-single", "G2-item", "G0-realtime", "G1c-realtime", "G-single-realtime",
+                 "G2-item-realtime")
+AP_TXN_DTYPE = np.dtype([("mop_off", "<i8"), ("inv_pos", "<i4"), ("comp_pos", "<i4"), ("type", "<i4"),
+                         ("mop_len", "<i4")])
+AP_MOP_DTYPE = np.dtype([("key", "<i8"), ("value", "<i8"), ("f", "<i4"), ("len", "<i4")])
+AP_EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("type", "<i4"), ("pad", "<i4"), ("key", "<i8")])
+AP_KEY_DTYPE = np.dtype([("key", "<i8"), ("longest", "<i8"), ("len", "<i4"), ("flags", "<i4"),
+                         ("first_dup", "<i4"), ("first_failed", "<i4"), ("first_phantom", "<i4"),
+                         ("pad", "<i4")])
+AP_STEP_DTYPE = np.dtype([("txn", "<i4"), ("type", "<i4"), ("key", "<i8")])
+assert (AP_TXN_DTYPE.itemsize, AP_MOP_DTYPE.itemsize, AP_EDGE_DTYPE.itemsize, AP_KEY_DTYPE.itemsize,
+        AP_STEP_DTYPE.itemsize) == (24, 24, 24, 40, 16)
+
+
+class LcApOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in
+                ("mop_flags", "txn_flags", "keys", "edges", "byc", "rt_lo", "rt_hi", "scc", "scc_class",
+                 "steps", "cycle_off", "cycle_scc")]
+
+
+class LcApSummary(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("n_incompatible_order", ctypes.c_int64), ("n_nonprefix", ctypes.c_int64),
+                ("n_duplicate", ctypes.c_int64), ("n_g1a", ctypes.c_int64), ("n_phantom", ctypes.c_int64),
+                ("n_g1b", ctypes.c_int64), ("n_internal", ctypes.c_int64), ("n_class", ctypes.c_int64 * 8),
+                ("n_keys", ctypes.c_int64), ("n_ok", ctypes.c_int64), ("n_nodes", ctypes.c_int64),
+                ("n_edges", ctypes.c_int64), ("n_scc", ctypes.c_int64),
+                ("n_cycles_returned", ctypes.c_int64), ("n_slow_reads", ctypes.c_int64),
+                ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("host_graph_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
+class LcApLimits(ctypes.Structure):
+    _fields_ = [("max_payload", ctypes.c_int64), ("default_max_payload", ctypes.c_int64),
+                ("max_position", ctypes.c_int64), ("max_mops", ctypes.c_int64)]
+
+
 class LcSynthParams(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("ops_per_key", ctypes.c_int64),
                 ("concurrency", ctypes.c_int32), ("n_values", ctypes.c_int32),
@@ -326,6 +373,14 @@ def lib():
             L.lc_set_full.restype = ctypes.c_int
             L.lc_set_full_limits.argtypes = [ctypes.POINTER(LcSfLimits)]
             L.lc_set_full_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_append_check"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            ap = [p, i64, p, i64, p, i64, ctypes.POINTER(LcApOut), ctypes.POINTER(LcApSummary)]
+            L.lc_append_check_host.argtypes = ap
+            L.lc_append_check_host.restype = ctypes.c_int
+            L.lc_append_check.argtypes = [vp] + ap
+            L.lc_append_check.restype = ctypes.c_int
+            L.lc_append_limits.argtypes = [ctypes.POINTER(LcApLimits)]
+            L.lc_append_limits.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -491,6 +546,66 @@ def set_full_limits():
     if rc != 0:
         raise LcError(rc, "lc_set_full_limits")
     return {f: getattr(s, f) for f, _ in LcSfLimits._fields_}
+
+
+class _AppendCall:
+    """One lc_append_check(_host) call's arrays: the inputs made contiguous,
+    the outputs allocated as the header sizes them."""
+
+    def __init__(self, txns, mops, values):
+        self.txns = np.ascontiguousarray(txns, dtype=AP_TXN_DTYPE)
+        self.mops = np.ascontiguousarray(mops, dtype=AP_MOP_DTYPE)
+        self.values = np.ascontiguousarray(values, dtype=np.int64)
+        nt, nm = max(len(self.txns), 1), max(len(self.mops), 1)
+        n_reads = int((self.mops["f"] == LC_AP_READ).sum())
+        i4 = lambda n: np.zeros(n, dtype=np.int32)  # noqa: E731
+        self.arrays = {
+            "mop_flags": i4(nm), "txn_flags": i4(nt), "keys": np.zeros(nm, dtype=AP_KEY_DTYPE),
+            "edges": np.zeros(max(n_reads + len(self.mops), 1), dtype=AP_EDGE_DTYPE),  # 2 reads + appends
+            "byc": i4(nt), "rt_lo": i4(nt), "rt_hi": i4(nt), "scc": i4(nt), "scc_class": i4(nt),
+            "steps": np.zeros(nt, dtype=AP_STEP_DTYPE),
+            "cycle_off": np.zeros(LC_AP_MAX_CYCLES + 1, dtype=np.int64), "cycle_scc": i4(LC_AP_MAX_CYCLES),
+        }
+        self.out = LcApOut(**{k: _ptr(v) for k, v in self.arrays.items()})
+        self.summary = LcApSummary()
+
+    def args(self):
+        return (_ptr(self.txns), len(self.txns), _ptr(self.mops), len(self.mops), _ptr(self.values),
+                len(self.values), ctypes.byref(self.out), ctypes.byref(self.summary))
+
+    def result(self):
+        """-> (a dict of the output arrays cut to their counts, the summary as a dict)."""
+        s = {}
+        for f, _ in LcApSummary._fields_:
+            v = getattr(self.summary, f)
+            s[f] = list(v) if f == "n_class" else v
+        a, nt, nm = self.arrays, len(self.txns), len(self.mops)
+        n_steps = int(a["cycle_off"][s["n_cycles_returned"]])
+        out = {"mop_flags": a["mop_flags"][:nm], "txn_flags": a["txn_flags"][:nt], "keys": a["keys"][:s["n_keys"]],
+               "edges": a["edges"][:s["n_edges"]], "byc": a["byc"][:s["n_ok"]], "rt_lo": a["rt_lo"][:nt],
+               "rt_hi": a["rt_hi"][:nt], "scc": a["scc"][:nt], "scc_class": a["scc_class"][:nt],
+               "steps": a["steps"][:n_steps], "cycle_off": a["cycle_off"][:s["n_cycles_returned"] + 1],
+               "cycle_scc": a["cycle_scc"][:s["n_cycles_returned"]]}
+        return out, s
+
+
+def append_check_host(txns, mops, values):
+    """lc_append_check_host: list-append's rules on the host -> (a dict of the
+    output arrays of include/lincheck_append.h's lc_ap_out, the summary as a dict)."""
+    call = _AppendCall(txns, mops, values)
+    rc = lib().lc_append_check_host(*call.args())
+    if rc != 0:
+        raise LcError(rc, "lc_append_check_host")
+    return call.result()
+
+
+def append_limits():
+    """lc_append_limits: {"max_payload", "default_max_payload", "max_position", "max_mops"}."""
+    s = LcApLimits()
+    rc = lib().lc_append_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_append_limits")
+    return {f: getattr(s, f) for f, _ in LcApLimits._fields_}
 
 
 class Context:
@@ -677,6 +792,14 @@ class Context:
         elif witness:
             ret = (rc, out, wit[:n_ops], kind)
         return ret + (pk.result(),) if packed else ret
+
+    def append_check(self, txns, mops, values):
+        """lc_append_check: append_check_host's result, with rules 1-6 on the device."""
+        call = _AppendCall(txns, mops, values)
+        rc = lib().lc_append_check(self._h, *call.args())
+        if rc != 0:
+            raise LcError(rc, self.last_error() if rc in (-22, -7) else "lc_append_check")
+        return call.result()
 
     def set_full(self, adds, reads, read_values, linearizable=True):
         """lc_set_full: set_full_host's result, computed on the device."""

@@ -1,0 +1,606 @@
+// append_host.cpp — lc_append_check_host: the rules of
+// include/lincheck_append.h on the host, single-threaded, with hash maps and
+// an iterative Tarjan; and the host parts of lc_append_check: the contract,
+// the slow path for reads the device could not decide, rule 6's host form,
+// rule 7 (SCCs, classes, witness cycles) and the summary.  g++, no GPU.
+#include <errno.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <chrono>
+#include <new>
+#include <unordered_map>
+#include <unordered_set>
+
+#include "append.h"
+
+namespace lcap {
+
+namespace {
+
+struct PairHash {
+  size_t operator()(const std::pair<int64_t, int64_t> &p) const { return (size_t)hash_pair(p.first, p.second); }
+};
+
+bool edge_less(const lc_ap_edge &a, const lc_ap_edge &b) {
+  if (a.from != b.from) return a.from < b.from;
+  if (a.to != b.to) return a.to < b.to;
+  if (a.type != b.type) return a.type < b.type;
+  return a.key < b.key;
+}
+
+bool edge_same(const lc_ap_edge &a, const lc_ap_edge &b) {
+  return a.from == b.from && a.to == b.to && a.type == b.type && a.key == b.key;
+}
+
+}  // namespace
+
+struct Writers::Impl {
+  std::unordered_map<std::pair<int64_t, int64_t>, int32_t, PairHash> map;
+};
+
+Writers::~Writers() { delete impl; }
+
+int Writers::build(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops) {
+  impl = new Impl;
+  last.assign((size_t)n_mops, 0);
+  std::unordered_set<int64_t> seen;
+  for (int64_t t = 0; t < n_txns; t++) {
+    seen.clear();
+    const int64_t b = txns[t].mop_off, e = b + txns[t].mop_len;
+    for (int64_t m = e - 1; m >= b; m--)
+      if (mops[m].f == LC_AP_APPEND && seen.insert(mops[m].key).second) last[m] = 1;
+    for (int64_t m = b; m < e; m++)
+      if (mops[m].f == LC_AP_APPEND && !impl->map.emplace(std::make_pair(mops[m].key, mops[m].value), (int32_t)m).second)
+        return -EINVAL;
+  }
+  return 0;
+}
+
+int32_t Writers::find(int64_t key, int64_t element) const {
+  const auto it = impl->map.find(std::make_pair(key, element));
+  return it == impl->map.end() ? -1 : it->second;
+}
+
+int prepare(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops, const int64_t *values,
+            int64_t n_values, const lc_ap_out *out, Prep *p, const char **err) {
+#define LCAP_BAD(text) \
+  do {                 \
+    *err = text;       \
+    return -EINVAL;    \
+  } while (0)
+  if (n_txns < 0 || n_mops < 0 || n_values < 0 || (n_txns > 0 && !txns) || (n_mops > 0 && !mops) ||
+      (n_values > 0 && !values))
+    LCAP_BAD("null array or negative count");
+  if (n_mops >= kMaxMops || n_txns >= kMaxMops) LCAP_BAD("2^31 - 1 or more txns or mops");
+  if (!out || !out->mop_flags || !out->txn_flags || !out->keys || !out->edges || !out->byc || !out->rt_lo ||
+      !out->rt_hi || !out->scc || !out->scc_class || !out->steps || !out->cycle_off || !out->cycle_scc)
+    LCAP_BAD("null out");
+  p->mop_txn.resize((size_t)n_mops);
+  p->txn_r0.resize((size_t)n_txns + 1);
+  p->work_off.assign(1, 0);
+  int64_t next = 0, prev_inv = -1;
+  for (int64_t t = 0; t < n_txns; t++) {
+    const lc_ap_txn &x = txns[t];
+    if (x.inv_pos <= prev_inv || x.inv_pos >= kMaxPosition) LCAP_BAD("txns not strictly ascending by inv_pos");
+    prev_inv = x.inv_pos;
+    if (x.type == LC_AP_INFO) {
+      if (x.comp_pos != -1) LCAP_BAD("an INFO txn with a comp_pos");
+    } else if (x.type == LC_AP_OK || x.type == LC_AP_FAIL) {
+      if (x.comp_pos <= x.inv_pos || x.comp_pos >= kMaxPosition) LCAP_BAD("comp_pos not above inv_pos");
+    } else {
+      LCAP_BAD("unknown txn type");
+    }
+    if (x.mop_off != next || x.mop_len < 0 || x.mop_len > n_mops - next)
+      LCAP_BAD("the txns' mop ranges do not tile the mops in order");
+    p->txn_r0[(size_t)t] = (int32_t)p->rd_mop.size();
+    for (int64_t m = next; m < next + x.mop_len; m++) {
+      const lc_ap_mop &o = mops[m];
+      p->mop_txn[(size_t)m] = (int32_t)t;
+      if (o.key == kReserved) LCAP_BAD("a key is INT64_MIN");
+      if (o.f == LC_AP_APPEND) {
+        if (o.value == kReserved) LCAP_BAD("an appended element is INT64_MIN");
+        p->n_appends++;
+      } else if (o.f == LC_AP_READ) {
+        p->n_reads++;
+        if (x.type == LC_AP_OK) {
+          if (o.len < 0 || o.value < 0 || o.value > n_values - o.len) LCAP_BAD("a read's payload leaves values");
+          p->rd_mop.push_back((int32_t)m);
+          p->work_off.push_back(p->work_off.back() + o.len);
+          if (p->work_off.back() >= kMaxMops) LCAP_BAD("the reads' total length is 2^31 - 1 or more");
+        } else if (o.len != -1) {
+          LCAP_BAD("a read of an INFO or FAIL txn with a len other than -1");
+        }
+      } else {
+        LCAP_BAD("unknown mop f");
+      }
+    }
+    next += x.mop_len;
+    if (x.type == LC_AP_OK) p->n_ok++;
+    if (x.type != LC_AP_FAIL) p->n_nodes++;
+  }
+  if (next != n_mops) LCAP_BAD("the txns' mop ranges do not tile the mops in order");
+  p->txn_r0[(size_t)n_txns] = (int32_t)p->rd_mop.size();
+  return 0;
+#undef LCAP_BAD
+}
+
+int32_t first_dup_direct(const int64_t *order, int32_t len) {
+  std::unordered_set<int64_t> seen;
+  for (int32_t i = 0; i < len; i++)
+    if (!seen.insert(order[i]).second) return i;
+  return -1;
+}
+
+int64_t rules34_direct(const lc_ap_txn *txns, const lc_ap_mop *mops, const int64_t *values, const Prep &p,
+                       const Writers &w, int64_t t, int32_t *mop_flags, int32_t *txn_flags) {
+  struct State {
+    int64_t read = -1;             // the latest read of the key in this txn
+    std::vector<int64_t> appends;  // own appends since (or since the txn began)
+  };
+  std::unordered_map<int64_t, State> state;
+  std::unordered_set<int64_t> seen;
+  int64_t n = 0;
+  int32_t tf = 0;
+  const int64_t b = txns[t].mop_off, e = b + txns[t].mop_len;
+  for (int64_t m = b; m < e; m++) {
+    const lc_ap_mop &o = mops[m];
+    State &s = state[o.key];
+    if (o.f == LC_AP_APPEND) {
+      s.appends.push_back(o.value);
+      continue;
+    }
+    if (o.len < 0) continue;
+    n++;
+    int32_t f = mop_flags[m] & LC_AP_R_NONPREFIX;
+    const int64_t *pl = values + o.value;
+    seen.clear();
+    for (int32_t i = 0; i < o.len; i++) {
+      if (!seen.insert(pl[i]).second) f |= LC_AP_R_DUPLICATE;
+      const int32_t wm = w.find(o.key, pl[i]);
+      if (wm < 0) f |= LC_AP_R_PHANTOM;
+      else if (txns[p.mop_txn[(size_t)wm]].type == LC_AP_FAIL) f |= LC_AP_R_G1A;
+    }
+    if (o.len > 0) {
+      const int32_t wm = w.find(o.key, pl[o.len - 1]);
+      if (wm >= 0 && p.mop_txn[(size_t)wm] != t && !w.last[(size_t)wm]) f |= LC_AP_R_G1B;
+    }
+    const int64_t a = (int64_t)s.appends.size();
+    bool ok = true;
+    if (s.read >= 0) {
+      const lc_ap_mop &q = mops[s.read];
+      ok = o.len == q.len + a && std::equal(pl, pl + q.len, values + q.value) &&
+           std::equal(s.appends.begin(), s.appends.end(), pl + q.len);
+    } else if (a > 0) {
+      ok = o.len >= a && std::equal(s.appends.begin(), s.appends.end(), pl + (o.len - a));
+    } else {
+      f |= LC_AP_R_EXTERNAL;
+    }
+    if (!ok) f |= LC_AP_R_INTERNAL;
+    s.read = m;
+    s.appends.clear();
+    mop_flags[m] = f;
+    tf |= f & LC_AP_R_ANOMALY;
+  }
+  txn_flags[t] = tf;
+  return n;
+}
+
+void real_time_host(const lc_ap_txn *txns, int64_t n_txns, int32_t *byc, int32_t *rt_lo, int32_t *rt_hi) {
+  int64_t n_ok = 0;
+  for (int64_t t = 0; t < n_txns; t++)
+    if (txns[t].type == LC_AP_OK) byc[n_ok++] = (int32_t)t;
+  std::stable_sort(byc, byc + n_ok, [&](int32_t a, int32_t b) { return txns[a].comp_pos < txns[b].comp_pos; });
+  std::vector<int32_t> comp((size_t)n_ok), pm((size_t)n_ok);
+  for (int64_t i = 0; i < n_ok; i++) {
+    comp[(size_t)i] = txns[byc[i]].comp_pos;
+    pm[(size_t)i] = std::max(i ? pm[(size_t)i - 1] : -1, txns[byc[i]].inv_pos);
+  }
+  for (int64_t t = 0; t < n_txns; t++) {
+    rt_lo[t] = rt_hi[t] = 0;
+    if (txns[t].type == LC_AP_FAIL) continue;
+    const int64_t hi = std::lower_bound(comp.begin(), comp.end(), txns[t].inv_pos) - comp.begin();
+    if (hi == 0) continue;
+    const int32_t m = pm[(size_t)hi - 1];
+    rt_lo[t] = (int32_t)(std::upper_bound(comp.begin(), comp.end(), m) - comp.begin());
+    rt_hi[t] = (int32_t)hi;
+  }
+}
+
+namespace {
+
+// The graph, walked against its edges: SCCs, cycles and "v reaches u" are the
+// same in the transposed graph, and a txn's real-time predecessors are a
+// range where its successors are not.
+struct Graph {
+  int64_t n;
+  const lc_ap_txn *txns;
+  const lc_ap_edge *edges;
+  int64_t n_edges;
+  const int32_t *byc, *lo, *hi;
+  std::vector<int64_t> in_off, out_off;  // edges by to (through in_idx) and by from (they are sorted so)
+  std::vector<int32_t> in_idx;
+  // scratch of scc(): index 0 means unvisited
+  std::vector<int32_t> index, low, comp, stack;
+  std::vector<uint8_t> on_stack;
+  std::vector<std::pair<int32_t, int64_t>> frames;
+  // scratch of the searches
+  std::vector<int32_t> mark, par, par_type, queue;
+  std::vector<int64_t> par_key;
+  int32_t mark_now = 0;
+
+  int64_t n_pred(int32_t b, int mask) const {
+    return in_off[(size_t)b + 1] - in_off[(size_t)b] + ((mask & 8) ? hi[b] - lo[b] : 0);
+  }
+  // the i-th predecessor of b under mask, or -1 where its edge is not in mask
+  int32_t pred(int32_t b, int mask, int64_t i, int32_t *type, int64_t *key) const {
+    const int64_t n_in = in_off[(size_t)b + 1] - in_off[(size_t)b];
+    if (i < n_in) {
+      const lc_ap_edge &e = edges[in_idx[(size_t)(in_off[(size_t)b] + i)]];
+      *type = e.type;
+      *key = e.key;
+      return ((mask >> e.type) & 1) ? e.from : -1;
+    }
+    *type = LC_AP_RT;
+    *key = 0;
+    return byc[lo[b] + (i - n_in)];
+  }
+
+  void init() {
+    in_off.assign((size_t)n + 1, 0);
+    out_off.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n_edges; i++) {
+      in_off[(size_t)edges[i].to + 1]++;
+      out_off[(size_t)edges[i].from + 1]++;
+    }
+    for (int64_t t = 0; t < n; t++) {
+      in_off[(size_t)t + 1] += in_off[(size_t)t];
+      out_off[(size_t)t + 1] += out_off[(size_t)t];
+    }
+    in_idx.resize((size_t)n_edges);
+    std::vector<int64_t> at(in_off.begin(), in_off.end() - 1);
+    for (int64_t i = 0; i < n_edges; i++) in_idx[(size_t)at[(size_t)edges[i].to]++] = (int32_t)i;
+    index.assign((size_t)n, 0);
+    low.assign((size_t)n, 0);
+    comp.assign((size_t)n, -1);
+    on_stack.assign((size_t)n, 0);
+    mark.assign((size_t)n, 0);
+    par.assign((size_t)n, -1);
+    par_type.assign((size_t)n, 0);
+    par_key.assign((size_t)n, 0);
+  }
+
+  // Tarjan, iterative, over `nodes` under mask, staying where region[x] ==
+  // tag (region null: everywhere).  comp[x] of every node is set to its
+  // component's number (0 .. return value - 1); index / low are left clean.
+  int32_t scc(const std::vector<int32_t> &nodes, int mask, const int32_t *region, int32_t tag) {
+    int32_t n_comp = 0, counter = 0;
+    for (int32_t root : nodes) {
+      if (index[(size_t)root]) continue;
+      frames.assign(1, {root, 0});
+      index[(size_t)root] = low[(size_t)root] = ++counter;
+      stack.push_back(root);
+      on_stack[(size_t)root] = 1;
+      while (!frames.empty()) {
+        const int32_t v = frames.back().first;
+        int64_t &i = frames.back().second;
+        if (i < n_pred(v, mask)) {
+          int32_t type;
+          int64_t key;
+          const int32_t u = pred(v, mask, i++, &type, &key);
+          if (u < 0 || (region && region[u] != tag)) continue;
+          if (!index[(size_t)u]) {
+            index[(size_t)u] = low[(size_t)u] = ++counter;
+            stack.push_back(u);
+            on_stack[(size_t)u] = 1;
+            frames.push_back({u, 0});
+          } else if (on_stack[(size_t)u]) {
+            low[(size_t)v] = std::min(low[(size_t)v], index[(size_t)u]);
+          }
+          continue;
+        }
+        if (low[(size_t)v] == index[(size_t)v]) {
+          int32_t x;
+          do {
+            x = stack.back();
+            stack.pop_back();
+            on_stack[(size_t)x] = 0;
+            comp[(size_t)x] = n_comp;
+          } while (x != v);
+          n_comp++;
+        }
+        frames.pop_back();
+        if (!frames.empty()) {
+          const int32_t up = frames.back().first;
+          low[(size_t)up] = std::min(low[(size_t)up], low[(size_t)v]);
+        }
+      }
+    }
+    for (int32_t x : nodes) index[(size_t)x] = low[(size_t)x] = 0;
+    return n_comp;
+  }
+
+  // Breadth first from u against the edges of mask, inside region[] == tag and
+  // comp[] == comp[u]:
+  // the first out-edge of u of type ct whose head v is met gives the cycle
+  // u -ct-> v -> ... -> u.  Its steps go to `steps`; false if there is none.
+  bool cycle_from(int32_t u, int ct, int mask, const int32_t *region, int32_t tag, std::vector<lc_ap_step> *steps) {
+    const int32_t cu = comp[(size_t)u];
+    int32_t now = ++mark_now;
+    // the candidates: heads of u's ct edges inside the component
+    bool any = false;
+    for (int64_t i = out_off[(size_t)u]; i < out_off[(size_t)u + 1]; i++)
+      if (edges[i].type == ct && region[edges[i].to] == tag && comp[(size_t)edges[i].to] == cu) any = true;
+    if (!any) return false;
+    queue.assign(1, u);
+    mark[(size_t)u] = now;
+    auto is_head = [&](int32_t x, int64_t *key) {
+      for (int64_t i = out_off[(size_t)u]; i < out_off[(size_t)u + 1]; i++)
+        if (edges[i].type == ct && edges[i].to == x) {
+          *key = edges[i].key;
+          return true;
+        }
+      return false;
+    };
+    for (size_t q = 0; q < queue.size(); q++) {
+      const int32_t b = queue[q];
+      const int64_t np = n_pred(b, mask);
+      for (int64_t i = 0; i < np; i++) {
+        int32_t type;
+        int64_t key;
+        const int32_t a = pred(b, mask, i, &type, &key);
+        if (a < 0 || region[a] != tag || comp[(size_t)a] != cu || mark[(size_t)a] == now) continue;
+        mark[(size_t)a] = now;
+        par[(size_t)a] = b;  // a -type/key-> b lies on a's way to u
+        par_type[(size_t)a] = type;
+        par_key[(size_t)a] = key;
+        int64_t ck;
+        if (is_head(a, &ck)) {
+          steps->push_back({u, ct, ck});
+          for (int32_t x = a; x != u; x = par[(size_t)x])
+            steps->push_back({x, par_type[(size_t)x], par_key[(size_t)x]});
+          return true;
+        }
+        queue.push_back(a);
+      }
+    }
+    return false;
+  }
+};
+
+}  // namespace
+
+void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
+                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum) {
+  const auto t0 = std::chrono::steady_clock::now();
+  lc_ap_summary s{};
+  Graph g;
+  g.n = n_txns;
+  g.txns = txns;
+  g.edges = out->edges;
+  g.n_edges = n_edges;
+  g.byc = out->byc;
+  g.lo = out->rt_lo;
+  g.hi = out->rt_hi;
+  g.init();
+  std::vector<int32_t> nodes;
+  nodes.reserve((size_t)p.n_nodes);
+  for (int64_t t = 0; t < n_txns; t++) {
+    out->scc[t] = out->scc_class[t] = -1;
+    if (txns[t].type != LC_AP_FAIL) nodes.push_back((int32_t)t);
+  }
+  const int32_t n_comp = g.scc(nodes, 15, nullptr, 0);
+  // the nontrivial components, numbered by their least txn
+  std::vector<int32_t> size((size_t)n_comp, 0), id((size_t)n_comp, -1);
+  for (int32_t x : nodes) size[(size_t)g.comp[(size_t)x]]++;
+  std::vector<std::vector<int32_t>> members;
+  for (int32_t x : nodes) {
+    const int32_t c = g.comp[(size_t)x];
+    if (size[(size_t)c] < 2) continue;
+    if (id[(size_t)c] < 0) {
+      id[(size_t)c] = (int32_t)members.size();
+      members.emplace_back();
+    }
+    out->scc[x] = id[(size_t)c];
+    members[(size_t)id[(size_t)c]].push_back(x);
+  }
+  static const int kCt[4] = {LC_AP_WW, LC_AP_WR, LC_AP_RW, LC_AP_RW};
+  static const int kMask[4] = {1, 3, 3, 7};
+  int64_t n_steps = 0, n_cycles = 0;
+  out->cycle_off[0] = 0;
+  std::vector<lc_ap_step> steps;
+  for (size_t c = 0; c < members.size(); c++) {
+    const std::vector<int32_t> &mem = members[c];
+    int32_t cls = -1;
+    steps.clear();
+    for (int k = 0; k < 8 && cls < 0; k++) {
+      const int ct = kCt[k & 3], mask = kMask[k & 3] | (k >= 4 ? 8 : 0);
+      // a cycle closed by a ct edge lies inside one component of mask + ct
+      g.scc(mem, mask | (1 << ct), out->scc, (int32_t)c);
+      for (int32_t u : mem)
+        if (g.cycle_from(u, ct, mask, out->scc, (int32_t)c, &steps)) {
+          cls = k;
+          break;
+        }
+    }
+    if (cls < 0) cls = LC_AP_G2_ITEM + LC_AP_REALTIME;  // (a nontrivial SCC is cyclic under every edge type)
+    for (int32_t x : mem) out->scc_class[x] = cls;
+    s.n_class[cls]++;
+    if (n_cycles < LC_AP_MAX_CYCLES) {
+      for (const lc_ap_step &st : steps) out->steps[n_steps++] = st;
+      out->cycle_scc[n_cycles] = (int32_t)c;
+      out->cycle_off[++n_cycles] = n_steps;
+    }
+  }
+  for (int64_t i = n_cycles; i < LC_AP_MAX_CYCLES; i++) {
+    out->cycle_off[i + 1] = n_steps;
+    out->cycle_scc[i] = -1;
+  }
+  for (int64_t k = 0; k < n_keys; k++)
+    if (out->keys[k].flags & LC_AP_K_INCOMPATIBLE) s.n_incompatible_order++;
+  s.n_nonprefix = n_nonprefix;
+  s.n_duplicate = counts[0];
+  s.n_g1a = counts[1];
+  s.n_phantom = counts[2];
+  s.n_g1b = counts[3];
+  s.n_internal = counts[4];
+  s.n_keys = n_keys;
+  s.n_ok = p.n_ok;
+  s.n_nodes = p.n_nodes;
+  s.n_edges = n_edges;
+  s.n_scc = (int64_t)members.size();
+  s.n_cycles_returned = n_cycles;
+  const bool bad = s.n_incompatible_order || s.n_nonprefix || s.n_duplicate || s.n_g1a || s.n_phantom || s.n_g1b ||
+                   s.n_internal || s.n_scc;
+  s.valid = p.n_ok == 0 ? -1 : bad ? 0 : 1;
+  s.host_graph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (sum) *sum = s;
+}
+
+}  // namespace lcap
+
+extern "C" int lc_append_limits(lc_ap_limit_info *out) {
+  if (!out) return -EINVAL;
+  out->default_max_payload = lcap::kDefaultMaxPayload;
+  out->max_payload = lcap::kDefaultMaxPayload;
+  if (const char *e = getenv("LC_AP_MAX_PAYLOAD")) {
+    const long long v = atoll(e);
+    if (v > 0) out->max_payload = v;
+  }
+  out->max_position = lcap::kMaxPosition;
+  out->max_mops = lcap::kMaxDeviceMops;
+  if (const char *e = getenv("LC_AP_MAX_MOPS")) {
+    const long long v = atoll(e);
+    if (v > 0 && v < lcap::kMaxDeviceMops) out->max_mops = v;
+  }
+  return 0;
+}
+
+namespace {
+
+int append_host(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops, const int64_t *values,
+                int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
+  using namespace lcap;
+  const auto t0 = std::chrono::steady_clock::now();
+  Prep p;
+  const char *why = nullptr;
+  if (int rc = prepare(txns, n_txns, mops, n_mops, values, n_values, out, &p, &why)) return rc;
+  Writers w;
+  if (int rc = w.build(txns, n_txns, mops, n_mops)) return rc;
+  const int64_t n_real = (int64_t)p.rd_mop.size();
+  // rule 2: the keys and their longest reads
+  struct Key {
+    int64_t key;
+    int32_t longest = -1, len = 0;  // a real read's ordinal
+  };
+  std::unordered_map<int64_t, int32_t> key_id;
+  std::vector<Key> keys;
+  std::vector<int32_t> mop_key((size_t)n_mops);
+  for (int64_t m = 0; m < n_mops; m++) {
+    const auto it = key_id.emplace(mops[m].key, (int32_t)keys.size());
+    if (it.second) keys.push_back(Key{mops[m].key});
+    mop_key[(size_t)m] = it.first->second;
+  }
+  for (int64_t r = 0; r < n_real; r++) {
+    Key &k = keys[(size_t)mop_key[(size_t)p.rd_mop[(size_t)r]]];
+    const int32_t len = mops[p.rd_mop[(size_t)r]].len;
+    if (k.longest < 0 || len > k.len) {
+      k.longest = (int32_t)r;
+      k.len = len;
+    }
+  }
+  std::vector<int32_t> order((size_t)keys.size());
+  for (size_t k = 0; k < keys.size(); k++) order[k] = (int32_t)k;
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return keys[(size_t)a].key < keys[(size_t)b].key; });
+  std::vector<int32_t> rank((size_t)keys.size());
+  for (size_t i = 0; i < order.size(); i++) rank[(size_t)order[i]] = (int32_t)i;
+  // the orders' writers and first_*
+  std::vector<std::vector<int32_t>> ord_w(keys.size());
+  for (size_t i = 0; i < order.size(); i++) {
+    const Key &k = keys[(size_t)order[i]];
+    lc_ap_key &o = out->keys[i];
+    o = lc_ap_key{k.key, -1, 0, 0, -1, -1, -1, 0};
+    if (k.longest < 0) continue;
+    const lc_ap_mop &rd = mops[p.rd_mop[(size_t)k.longest]];
+    o.longest = p.rd_mop[(size_t)k.longest];
+    o.len = rd.len;
+    o.first_dup = first_dup_direct(values + rd.value, rd.len);
+    std::vector<int32_t> &wr = ord_w[(size_t)order[i]];
+    wr.resize((size_t)rd.len);
+    for (int32_t j = 0; j < rd.len; j++) {
+      const int32_t wm = w.find(k.key, values[rd.value + j]);
+      wr[(size_t)j] = wm;
+      if (wm < 0 && o.first_phantom < 0) o.first_phantom = j;
+      if (wm >= 0 && txns[p.mop_txn[(size_t)wm]].type == LC_AP_FAIL && o.first_failed < 0) o.first_failed = j;
+    }
+  }
+  // prefix reads
+  for (int64_t m = 0; m < n_mops; m++) out->mop_flags[m] = 0;
+  int64_t n_nonprefix = 0;
+  for (int64_t r = 0; r < n_real; r++) {
+    const int32_t m = p.rd_mop[(size_t)r];
+    const int32_t kid = mop_key[(size_t)m];
+    const lc_ap_mop &lg = mops[p.rd_mop[(size_t)keys[(size_t)kid].longest]];
+    if (!std::equal(values + mops[m].value, values + mops[m].value + mops[m].len, values + lg.value)) {
+      out->mop_flags[m] = LC_AP_R_NONPREFIX;
+      out->keys[rank[(size_t)kid]].flags |= LC_AP_K_INCOMPATIBLE;
+      n_nonprefix++;
+    }
+  }
+  for (size_t i = 0; i < order.size(); i++) {
+    lc_ap_key &o = out->keys[i];
+    if ((o.flags & LC_AP_K_INCOMPATIBLE) || o.first_dup >= 0 || o.first_phantom >= 0) o.flags |= LC_AP_K_NO_ORDER;
+  }
+  // rules 3 and 4
+  int64_t counts[kCounters] = {0};
+  for (int64_t t = 0; t < n_txns; t++) {
+    out->txn_flags[t] = 0;
+    if (txns[t].type != LC_AP_OK) continue;
+    rules34_direct(txns, mops, values, p, w, t, out->mop_flags, out->txn_flags);
+    for (int64_t m = txns[t].mop_off; m < txns[t].mop_off + txns[t].mop_len; m++)
+      for (int b = 0; b < 5; b++) counts[b] += (out->mop_flags[m] >> (b + 1)) & 1;
+  }
+  // rule 5
+  auto node_of = [&](int32_t wm) {
+    const int32_t t = p.mop_txn[(size_t)wm];
+    return txns[t].type == LC_AP_FAIL ? -1 : t;
+  };
+  int64_t n_edges = 0;
+  auto emit = [&](int32_t from, int32_t to, int32_t type, int64_t key) {
+    if (from >= 0 && to >= 0 && from != to) out->edges[n_edges++] = lc_ap_edge{from, to, type, 0, key};
+  };
+  for (size_t i = 0; i < order.size(); i++) {
+    if (out->keys[i].flags & LC_AP_K_NO_ORDER) continue;
+    const std::vector<int32_t> &wr = ord_w[(size_t)order[i]];
+    for (size_t j = 0; j + 1 < wr.size(); j++) emit(node_of(wr[j]), node_of(wr[j + 1]), LC_AP_WW, out->keys[i].key);
+  }
+  for (int64_t r = 0; r < n_real; r++) {
+    const int32_t m = p.rd_mop[(size_t)r];
+    const int32_t kid = mop_key[(size_t)m];
+    if ((out->keys[rank[(size_t)kid]].flags & LC_AP_K_NO_ORDER) || !(out->mop_flags[m] & LC_AP_R_EXTERNAL)) continue;
+    const std::vector<int32_t> &wr = ord_w[(size_t)kid];
+    const int32_t len = mops[m].len, t = p.mop_txn[(size_t)m];
+    if (len > 0) emit(node_of(wr[(size_t)len - 1]), t, LC_AP_WR, mops[m].key);
+    if ((size_t)len < wr.size()) emit(t, node_of(wr[(size_t)len]), LC_AP_RW, mops[m].key);
+  }
+  std::sort(out->edges, out->edges + n_edges, edge_less);
+  n_edges = std::unique(out->edges, out->edges + n_edges, edge_same) - out->edges;
+  real_time_host(txns, n_txns, out->byc, out->rt_lo, out->rt_hi);
+  lc_ap_summary s;
+  graph_and_summary(txns, n_txns, p, out, (int64_t)keys.size(), n_edges, n_nonprefix, counts, &s);
+  s.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (sum) *sum = s;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int lc_append_check_host(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
+                                    const int64_t *values, int64_t n_values, const lc_ap_out *out,
+                                    lc_ap_summary *sum) {
+  try {
+    return append_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
+  } catch (const std::bad_alloc &) {
+    return -ENOMEM;
+  }
+}

@@ -35,6 +35,7 @@
 #include "counted.h"
 #include "events.h"
 #include "setfull.h"
+#include "append.h"
 
 #ifndef LC_BUILD_ID
 #define LC_BUILD_ID "unknown"
@@ -244,6 +245,24 @@ struct SfState {
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
 };
 
+// lc_append_check: its workspace on the context's first device (grown on
+// demand, freed at lc_close).
+struct ApState {
+  Buf<lc_ap_txn> d_txns;
+  Buf<lc_ap_mop> d_mops;
+  Buf<int64_t> d_values, d_work_off, d_ktab, d_counters, d_count;
+  Buf<int32_t> d_mop_txn, d_rd_mop, d_txn_r0, d_stamp, d_kfirst, d_kflags, d_mop_kslot, d_ord_w, d_mop_flags,
+      d_txn_flags, d_status, d_kslots,
+      d_rt;  // d_rt: 7 arrays of n_txns (launch_real_time's, then rt_lo, rt_hi)
+  Buf<unsigned long long> d_wtab, d_kbest;
+  Buf<uint8_t> d_mop_last, d_nonprefix, d_temp;
+  Buf<lc_ap_edge> d_slots, d_edges_a, d_edges_b;
+  Buf<lc_ap_key> d_keys;
+  int64_t *h_small = nullptr;  // pinned: the status words, the four counts, then the counters
+  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
+};
+
 }  // namespace
 
 struct lc_ctx {
@@ -262,6 +281,7 @@ struct lc_ctx {
   lc_call_profile prof{};  // lc_last_call_profile
   EvState evs;             // lc_check_events
   SfState sfs;             // lc_set_full
+  ApState aps;             // lc_append_check
 };
 
 namespace {
@@ -2572,6 +2592,226 @@ int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_s
   return 0;
 }
 
+// lc_append_check: the arrays copied to the context's first device; rules 1
+// to 6 there (append.hip); the reads the device left open, rule 7 and the
+// summary on the host (append_host.cpp).
+int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
+                  const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
+  const auto t0 = std::chrono::steady_clock::now();
+  lcap::Prep p;
+  const char *why = nullptr;
+  if (lcap::prepare(txns, n_txns, mops, n_mops, values, n_values, out, &p, &why)) {
+    set_err(c, std::string("lc_append_check: ") + why);
+    return -EINVAL;
+  }
+  if (n_txns == 0) return lc_append_check_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
+  const size_t nt = (size_t)n_txns, nm = (size_t)n_mops, nr = p.rd_mop.size();
+  const int64_t n_work = p.work_off[nr];
+  lc_ap_limit_info lim;
+  lc_append_limits(&lim);
+  if (n_values > lim.max_payload || n_work > lim.max_payload) {
+    set_err(c, "lc_append_check: the payload exceeds lc_append_limits' max_payload");
+    return -E2BIG;
+  }
+  if (n_mops > lim.max_mops) {  // (the key table's slot index is an int32)
+    set_err(c, "lc_append_check: more mops than lc_append_limits' max_mops");
+    return -E2BIG;
+  }
+  ApState &s = c->aps;
+  Dev &d = c->devs[0];
+  HIP_TRY(c, hipSetDevice(d.id));
+  (void)settle_status(d);
+  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
+  hipStream_t st = d.stream;
+  constexpr size_t kCountersLen = lcap::kCounters * lcap::kCounterShards * lcap::kCounterStride;
+  constexpr size_t kSmall = 6 + kCountersLen;  // in int64: 4 status words, 4 counts, the counters
+  if (!s.e0) {
+    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2, &s.k0, &s.k1, &s.k2}) HIP_TRY(c, hipEventCreate(e));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
+  }
+  const uint64_t wcap = lcap::table_capacity(p.n_appends), kcap = lcap::table_capacity(n_mops);
+  const size_t n_slots = 2 * nr + (size_t)n_work, n_edge_room = 2 * nr + (size_t)p.n_appends;
+  const size_t temp_bytes = std::max({lcap::edge_temp_bytes((int64_t)n_slots), lcap::rt_temp_bytes(n_txns),
+                                      lcap::key_temp_bytes(kcap)});
+  int e = ensure(c, s.d_txns, sizeof(lc_ap_txn) * nt);
+  if (!e) e = ensure(c, s.d_mops, sizeof(lc_ap_mop) * nm);
+  if (!e) e = ensure(c, s.d_values, sizeof(int64_t) * (size_t)n_values);
+  if (!e) e = ensure(c, s.d_work_off, sizeof(int64_t) * (nr + 1));
+  if (!e) e = ensure(c, s.d_mop_txn, sizeof(int32_t) * nm);
+  if (!e) e = ensure(c, s.d_rd_mop, sizeof(int32_t) * nr);
+  if (!e) e = ensure(c, s.d_txn_r0, sizeof(int32_t) * (nt + 1));
+  if (!e) e = ensure(c, s.d_wtab, sizeof(unsigned long long) * wcap);
+  if (!e) e = ensure(c, s.d_stamp, sizeof(int32_t) * wcap);
+  if (!e) e = ensure(c, s.d_ktab, sizeof(int64_t) * kcap);
+  if (!e) e = ensure(c, s.d_kbest, sizeof(unsigned long long) * kcap);
+  if (!e) e = ensure(c, s.d_kfirst, sizeof(int32_t) * 3 * kcap);
+  if (!e) e = ensure(c, s.d_kflags, sizeof(int32_t) * kcap);
+  if (!e) e = ensure(c, s.d_mop_kslot, sizeof(int32_t) * nm);
+  if (!e) e = ensure(c, s.d_mop_last, nm);
+  if (!e) e = ensure(c, s.d_ord_w, sizeof(int32_t) * (size_t)n_work);
+  if (!e) e = ensure(c, s.d_nonprefix, nr);
+  if (!e) e = ensure(c, s.d_mop_flags, sizeof(int32_t) * nm);
+  if (!e) e = ensure(c, s.d_txn_flags, sizeof(int32_t) * nt);
+  if (!e) e = ensure(c, s.d_slots, sizeof(lc_ap_edge) * n_slots);
+  // rule 5 bounds the set slots by n_edge_room: the wr / rw slots are two per read, and a ww slot is
+  // set only inside an order without repeats and phantoms, whose entries are distinct appends of its key
+  if (!e) e = ensure(c, s.d_edges_a, sizeof(lc_ap_edge) * n_edge_room);
+  if (!e) e = ensure(c, s.d_edges_b, sizeof(lc_ap_edge) * n_edge_room);
+  if (!e) e = ensure(c, s.d_kslots, sizeof(int32_t) * kcap);
+  if (!e) e = ensure(c, s.d_keys, sizeof(lc_ap_key) * nm);
+  if (!e) e = ensure(c, s.d_counters, sizeof(int64_t) * kCountersLen);
+  if (!e) e = ensure(c, s.d_count, sizeof(int64_t) * 4);
+  if (!e) e = ensure(c, s.d_status, sizeof(int32_t) * 4);
+  if (!e) e = ensure(c, s.d_rt, sizeof(int32_t) * 7 * nt);
+  if (!e) e = ensure(c, s.d_temp, temp_bytes);
+  if (e) return e;
+  HIP_TRY(c, hipEventRecord(s.e0, st));
+  HIP_TRY(c, hipMemcpyAsync(s.d_txns.p, txns, sizeof(lc_ap_txn) * nt, hipMemcpyHostToDevice, st));
+  if (nm) {
+    HIP_TRY(c, hipMemcpyAsync(s.d_mops.p, mops, sizeof(lc_ap_mop) * nm, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(s.d_mop_txn.p, p.mop_txn.data(), sizeof(int32_t) * nm, hipMemcpyHostToDevice, st));
+  }
+  if (n_values)
+    HIP_TRY(c, hipMemcpyAsync(s.d_values.p, values, sizeof(int64_t) * (size_t)n_values, hipMemcpyHostToDevice, st));
+  if (nr) HIP_TRY(c, hipMemcpyAsync(s.d_rd_mop.p, p.rd_mop.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(s.d_txn_r0.p, p.txn_r0.data(), sizeof(int32_t) * (nt + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(s.d_work_off.p, p.work_off.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice,
+                            st));
+  HIP_TRY(c, hipEventRecord(s.e1, st));
+  // nothing of an earlier call survives: empty tables (every empty word is
+  // all ones), no flags, no edge slots, no counts
+  HIP_TRY(c, hipMemsetAsync(s.d_wtab.p, 0xFF, sizeof(unsigned long long) * wcap, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_stamp.p, 0xFF, sizeof(int32_t) * wcap, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_ktab.p, 0xFF, sizeof(int64_t) * kcap, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_kbest.p, 0, sizeof(unsigned long long) * kcap, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_kfirst.p, 0xFF, sizeof(int32_t) * 3 * kcap, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_kflags.p, 0, sizeof(int32_t) * kcap, st));
+  if (nm) HIP_TRY(c, hipMemsetAsync(s.d_mop_flags.p, 0, sizeof(int32_t) * nm, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_txn_flags.p, 0, sizeof(int32_t) * nt, st));  // (no kernel writes them without mops)
+  if (nm) HIP_TRY(c, hipMemsetAsync(s.d_mop_last.p, 0, nm, st));
+  if (nr) HIP_TRY(c, hipMemsetAsync(s.d_nonprefix.p, 0, nr, st));
+  if (n_slots) HIP_TRY(c, hipMemsetAsync(s.d_slots.p, 0xFF, sizeof(lc_ap_edge) * n_slots, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_counters.p, 0, sizeof(int64_t) * kCountersLen, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_count.p, 0, sizeof(int64_t) * 4, st));
+  HIP_TRY(c, hipMemsetAsync(s.d_status.p, 0, sizeof(int32_t) * 4, st));
+  lcap::Ws w{};
+  w.txns = s.d_txns.p;
+  w.mops = s.d_mops.p;
+  w.values = s.d_values.p;
+  w.mop_txn = s.d_mop_txn.p;
+  w.rd_mop = s.d_rd_mop.p;
+  w.txn_r0 = s.d_txn_r0.p;
+  w.work_off = s.d_work_off.p;
+  w.n_txns = n_txns;
+  w.n_mops = n_mops;
+  w.n_real = (int64_t)nr;
+  w.n_work = n_work;
+  w.wtab = s.d_wtab.p;
+  w.stamp = s.d_stamp.p;
+  w.wcap = wcap;
+  w.ktab = s.d_ktab.p;
+  w.kbest = s.d_kbest.p;
+  w.kfirst = s.d_kfirst.p;
+  w.kflags = s.d_kflags.p;
+  w.kcap = kcap;
+  w.mop_kslot = s.d_mop_kslot.p;
+  w.mop_last = s.d_mop_last.p;
+  w.ord_w = s.d_ord_w.p;
+  w.nonprefix = s.d_nonprefix.p;
+  w.mop_flags = s.d_mop_flags.p;
+  w.txn_flags = s.d_txn_flags.p;
+  w.slots = s.d_slots.p;
+  w.keys = s.d_keys.p;
+  w.counters = s.d_counters.p;
+  w.status = s.d_status.p;
+  int32_t *rt = s.d_rt.p;  // ok_idx, ok_comp, byc, comp_sorted, pm, rt_lo, rt_hi
+  int32_t *d_byc = rt + 2 * nt, *d_lo = rt + 5 * nt, *d_hi = rt + 6 * nt;
+  HIP_TRY(c, hipEventRecord(s.k0, st));
+  if (nm) HIP_TRY(c, lcap::launch_rules(w, s.d_kslots.p, s.d_count.p + 3, s.d_temp.p, temp_bytes, st));
+  if (n_slots) HIP_TRY(c, lcap::launch_edge_select(w, s.d_edges_a.p, s.d_count.p, s.d_temp.p, temp_bytes, st));
+  HIP_TRY(c, lcap::launch_real_time(w, p.n_ok, rt, rt + nt, d_byc, rt + 3 * nt, rt + 4 * nt, d_lo, d_hi,
+                                    s.d_count.p + 2, s.d_temp.p, temp_bytes, st));
+  HIP_TRY(c, hipEventRecord(s.k1, st));
+  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
+  int64_t *h_count = s.h_small + 2, *h_counters = s.h_small + 6;  // counts: set slots, edges, (OK txns), keys
+  HIP_TRY(c, hipMemcpyAsync(h_status, s.d_status.p, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h_count, s.d_count.p, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h_counters, s.d_counters.p, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (h_status[0]) {
+    set_err(c, "lc_append_check: two appends of one (key, element) (mop " + std::to_string(h_status[1]) + " is one)");
+    return -EINVAL;
+  }
+  const int64_t n_sel = h_count[0], n_keys = h_count[3];
+  if (n_sel > (int64_t)n_edge_room || n_keys > n_mops) {  // (more edges than rule 5 allows: a bug, not an input)
+    set_err(c, "lc_append_check: inconsistent edge or key count");
+    return -EIO;
+  }
+  h_count[1] = 0;
+  HIP_TRY(c, hipEventRecord(s.k2, st));
+  if (n_sel > 0) {
+    HIP_TRY(c, lcap::launch_edge_sort(s.d_edges_a.p, s.d_edges_b.p, n_sel, s.d_count.p + 1, s.d_temp.p, temp_bytes,
+                                      st));
+  }
+  HIP_TRY(c, hipEventRecord(s.e2, st));
+  if (n_sel > 0) HIP_TRY(c, hipMemcpyAsync(h_count + 1, s.d_count.p + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  if (nm) HIP_TRY(c, hipMemcpyAsync(out->mop_flags, s.d_mop_flags.p, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->txn_flags, s.d_txn_flags.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  if (n_keys)
+    HIP_TRY(c, hipMemcpyAsync(out->keys, s.d_keys.p, sizeof(lc_ap_key) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
+  if (p.n_ok) HIP_TRY(c, hipMemcpyAsync(out->byc, d_byc, sizeof(int32_t) * (size_t)p.n_ok, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->rt_lo, d_lo, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->rt_hi, d_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  const int64_t n_edges = h_count[1];
+  if (n_edges > 0) {  // only the unique edges reach the caller
+    HIP_TRY(c, hipMemcpyAsync(out->edges, s.d_edges_a.p, sizeof(lc_ap_edge) * (size_t)n_edges, hipMemcpyDeviceToHost,
+                              st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+  }
+  // the key records: ascending by key; first_dup of an order with two
+  // phantoms from its definition (the device sees repeats of written elements)
+  std::sort(out->keys, out->keys + n_keys, [](const lc_ap_key &a, const lc_ap_key &b) { return a.key < b.key; });
+  for (int64_t k = 0; k < n_keys; k++) {
+    lc_ap_key &kr = out->keys[k];
+    if (!(kr.flags & lcap::kKeyTwoPhantoms)) continue;
+    kr.flags &= ~lcap::kKeyTwoPhantoms;
+    kr.first_dup = lcap::first_dup_direct(values + mops[kr.longest].value, kr.len);
+  }
+  // exact but not fast: the txns the device left open (a history without
+  // non-prefix reads and twice-phantom orders has none)
+  int64_t counts[lcap::kCounters] = {0}, n_nonprefix = 0;
+  for (int b = 0; b < lcap::kCounters; b++)
+    for (int i = 0; i < lcap::kCounterShards; i++)
+      counts[b] += h_counters[((size_t)b * lcap::kCounterShards + i) * lcap::kCounterStride];
+  const int64_t n_slow = counts[5];
+  if (n_slow) {
+    lcap::Writers wr;
+    if (wr.build(txns, n_txns, mops, n_mops)) {
+      set_err(c, "lc_append_check: the host found two appends of one pair where the device found none");
+      return -EIO;
+    }
+    for (int64_t t = 0; t < n_txns; t++) {
+      if (!(out->txn_flags[t] & lcap::kTxnSlow)) continue;
+      lcap::rules34_direct(txns, mops, values, p, wr, t, out->mop_flags, out->txn_flags);
+      for (int64_t m = txns[t].mop_off; m < txns[t].mop_off + txns[t].mop_len; m++) {
+        n_nonprefix += out->mop_flags[m] & LC_AP_R_NONPREFIX;
+        for (int b = 0; b < 5; b++) counts[b] += (out->mop_flags[m] >> (b + 1)) & 1;
+      }
+    }
+  }
+  lc_ap_summary sm;
+  lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm);
+  sm.n_slow_reads = n_slow;
+  float ms = 0;
+  sm.h2d_ms = hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess ? ms : 0;
+  sm.kernel_ms = hipEventElapsedTime(&ms, s.k0, s.k1) == hipSuccess ? ms : 0;
+  if (hipEventElapsedTime(&ms, s.k2, s.e2) == hipSuccess) sm.kernel_ms += ms;
+  sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (sum) *sum = sm;
+  return 0;
+}
+
 // lc_events_pack / lc_check_events: the events copied to the context's first
 // device and split, completed and packed there (events.hip).  On return the
 // stream has drained, s.h_status holds the call's counts, and the records
@@ -2836,6 +3076,17 @@ void lc_close(lc_ctx *c) {
       if (b) (void)hipFree(b);
     if (f.h_small) (void)hipHostFree(f.h_small);
     for (hipEvent_t e : {f.e0, f.e1, f.e2})
+      if (e) (void)hipEventDestroy(e);
+    // every Buf of ApState
+    ApState &a = c->aps;
+    for (void *b : std::initializer_list<void *>{
+             a.d_txns.p, a.d_mops.p, a.d_values.p, a.d_work_off.p, a.d_ktab.p, a.d_counters.p, a.d_count.p,
+             a.d_mop_txn.p, a.d_rd_mop.p, a.d_txn_r0.p, a.d_stamp.p, a.d_kfirst.p, a.d_kflags.p, a.d_mop_kslot.p,
+             a.d_ord_w.p, a.d_mop_flags.p, a.d_txn_flags.p, a.d_status.p, a.d_kslots.p, a.d_rt.p, a.d_wtab.p, a.d_kbest.p,
+             a.d_mop_last.p, a.d_nonprefix.p, a.d_temp.p, a.d_slots.p, a.d_edges_a.p, a.d_edges_b.p, a.d_keys.p})
+      if (b) (void)hipFree(b);
+    if (a.h_small) (void)hipHostFree(a.h_small);
+    for (hipEvent_t e : {a.e0, a.e1, a.e2, a.k0, a.k1, a.k2})
       if (e) (void)hipEventDestroy(e);
   }
   for (auto &f : c->fxs) lc_fx_close(f.first);
@@ -3263,6 +3514,17 @@ int lc_set_full(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_re
     return set_full_device(c, adds, n_adds, reads, n_reads, read_values, n_values, linearizable, out, sum);
   } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
     set_err(c, "lc_set_full: out of host memory");
+    return -ENOMEM;
+  }
+}
+
+int lc_append_check(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
+                    const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
+  if (!c) return -EINVAL;
+  try {
+    return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum);
+  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
+    set_err(c, "lc_append_check: out of host memory");
     return -ENOMEM;
   }
 }
