@@ -12,6 +12,10 @@
 // LDS.  No collective is needed: keys are independent and results land in
 // the caller's array.  There is no CPU fallback: without a usable GPU lc_open
 // fails with -ENODEV.
+//
+// This file is the register path and the context.  The side checkers
+// (lc_check_events, lc_set_full, lc_append_check) have their drivers in
+// *_dev.cpp; runtime.h is what those share with this file.
 #include <errno.h>
 #include <hip/hip_runtime.h>
 
@@ -33,13 +37,13 @@
 #include "../../../include/lincheck_fx.h"
 #include "kernels.h"
 #include "counted.h"
-#include "events.h"
-#include "setfull.h"
-#include "append.h"
+#include "runtime.h"
 
 #ifndef LC_BUILD_ID
 #define LC_BUILD_ID "unknown"
 #endif
+
+using namespace lcrt;
 
 namespace {
 
@@ -104,217 +108,14 @@ constexpr int64_t kGapWaveMinKeys = 1024;             // ... when there are more
 constexpr int64_t kGapWideMaxKeys = 64;    // at most this many keys for the gap tier ...
 constexpr int kGapWideMinLen = 2048;        // ... the longest of them this long: 512-thread workgroups
 
-// A device buffer with its capacity in bytes (ensure(): at least 256 bytes,
-// grow-only, freed at lc_close).  No destructor: lc_open copies a Dev into
-// lc_ctx::devs, and lc_close frees every buffer once.
-template <class T>
-struct Buf {
-  T *p = nullptr;
-  size_t cap = 0;
-};
-
-struct Dev {
-  int id = -1;
-  hipStream_t stream = nullptr;
-
-  // ---- device buffers (each is named once more, in lc_close's list) ----
-  Buf<lc_op> d_ops;
-  Buf<int64_t> d_off;
-  Buf<lc_key_result> d_out;
-  Buf<int32_t> d_ovf, d_ovf2;
-  Buf<int32_t> d_jit;
-  Buf<int32_t> d_flags;         // per key: handed over by the fast tier (zero between calls)
-  Buf<int32_t> d_jit2;          // keys the gap tier passes on
-  Buf<int32_t> d_gap2;          // keys the crash-light pass leaves to the gap tier
-  Buf<int32_t> d_gws;           // gap-tier workspace
-  Buf<char> d_cex;              // gap-tier counterexample intervals + probes
-  Buf<void> d_ws;               // HBM tiers' workspace
-  Buf<int32_t> d_wit, d_kind;   // lc_check_ex: device copies of the lc_aux outputs
-  Buf<int32_t> d_cert, d_cset;  // lc_aux certificates (4 per key), their position sets
-  Buf<int32_t> d_cws;           // certificate workspace
-  Buf<char> d_ops32;            // copy pipeline: lc_check32 / lc_check16's staging records
-  Buf<int64_t> d_base;          // ... and the keys' bases
-  Buf<lcdev::WitnessStatus> d_wst;  // LC_FLAG_SEARCH_WITNESS: the stage's status words
-
-  // ---- events ----
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-  hipEvent_t ef = nullptr;                  // after the first pass
-  hipEvent_t el = nullptr;                  // after the crash-light pass
-  hipEvent_t eg = nullptr;                  // after the gap tier
-  hipEvent_t eh0 = nullptr, eh1 = nullptr;  // around lc_check's host-to-device copies
-
-  // ---- status words, and what the next call has to know about them ----
-  lcdev::KStatus *d_status = nullptr;   // all-zero between calls
-  lcdev::KStatus *h_status = nullptr;   // pinned: D2H copies of d_status
-  int32_t *h_handoff = nullptr;         // host-coherent: [0] fast tier handed keys over, [1] a fused
-                                        // pass's crash-light key count (status_settle_kernel)
-  int32_t *h_handoff_dev = nullptr;     // its device address
-  bool status_dirty = true;             // d_status may be non-zero
-  // the handoff flags may be non-zero (the fast tier raised some and no
-  // compaction, which clears them, followed)
-  bool flags_dirty = true;
-  // A fused call that handed nothing over copies its status without waiting
-  // for it (the counts only choose the next call's pass and fill this call's
-  // n_gap_keys): the next call, or lc_last_stats, settles it (settle_status).
-  hipEvent_t es = nullptr;
-  bool st_pending = false;
-  int64_t st_keys = 0;
-  bool use_fused = false;  // the next call takes the fused version-order + crash-light pass
-  // some key of the last run_device call may be LC_INVALID (a key was handed
-  // over past the version-order tier, which decides valid keys only): the
-  // certificate pass runs only then
-  bool maybe_invalid = true;
-
-  // ---- completion signal ----
-  // The version-order / fused pass's follower signal (kernels.h
-  // launch_done_signal): a host-mapped word the host spins on instead of
-  // waiting for an event; the pass's HIP-event time is read later
-  // (timing_pending)
-  uint32_t *h_done = nullptr, *h_done_dev = nullptr;
-  uint32_t seq = 0;
-  bool timing_pending = false;
-
-  // ---- resident grid ----
-  // the resident version-order grid (kernels.h launch_fast_resident), on its
-  // own stream; res_grid: workgroups of the live grid (0: none)
-  lcdev::ResHost *res_h = nullptr, *res_h_dev = nullptr;
-  lcdev::ResDev *res_d = nullptr;
-  hipStream_t rst = nullptr;
-  int64_t res_grid = 0;
-  uint32_t res_seq = 0;
-  int res_khz = 0;          // the device's wall-clock rate
-  int64_t res_idle_us = 50; // LC_RESIDENT_IDLE_US (read at each grid launch)
-  int64_t res_cap = -1;     // lcdev::fast_resident_capacity() (once)
-  bool res_broken = false;  // a request the grid did not complete: launches only from then on
-
-  // ---- copy pipeline ----
-  // lc_check's host-to-device pipeline: the copy streams and one event per
-  // chunk (its records landed); the staging records are d_ops32 / d_base
-  // (two copy streams, chunks alternating: two DMA engines read host memory
-  // at once; measured 52-53 GB/s with one, 57 GB/s with two on one GPU)
-  hipStream_t cst = nullptr, cst2 = nullptr;
-  std::vector<hipEvent_t> cev;
-  // lc_check's small calls from pageable memory: inputs and outputs pass
-  // through this pinned buffer (kStageMax)
-  char *h_stage = nullptr;
-
-  // ---- statistics ----
-  double kernel_ms = 0, fast_ms = 0, gap_ms = 0, jit_ms = 0, hbm_ms = 0;
-  int64_t n_gap = 0, n_jit = 0, n_hbm = 0;
-  int malformed = 0;
-  lc_counted_stats counted{};               // this device's share of lc_last_counted_stats
-  lc_witness_stats wit{};                   // this device's share of lc_last_witness_stats
-  lc_counted_witness_stats cwit{};          // this device's share of lc_last_counted_witness_stats
-  lc_device_stats last{};                   // this device's share of the last lc_check
-  double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
-  // this device's share of lc_last_totals: written only by the device's own
-  // thread during a call (check_host runs one per device), summed by
-  // lc_last_totals after the threads are joined
-  lc_totals tot{};
-};
-
-// lc_check_events / lc_events_pack: the event path's own workspace on the
-// context's first device (grown on demand, freed at lc_close) and the last
-// call's statistics.
-struct EvState {
-  Buf<lc_event> d_ev;
-  Buf<int32_t> d_cnt, d_cursor, d_match, d_nops, d_nfail, d_nign, d_completion;
-  Buf<int64_t> d_seg_off, d_key_off, d_key_base;
-  Buf<uint32_t> d_seg;
-  Buf<unsigned long long> d_gtab;
-  Buf<lc_op32> d_ops32;
-  Buf<lc_key_result> d_res;
-  Buf<lcev::Status> d_status;
-  lcev::Status *h_status = nullptr;  // pinned
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-  lc_events_stats stats{};
-};
-
-// lc_set_full: its workspace on the context's first device (grown on demand,
-// freed at lc_close).
-struct SfState {
-  Buf<lc_sf_add> d_adds;
-  Buf<lc_sf_read> d_reads;
-  Buf<int64_t> d_values, d_work_off, d_tab_key, d_counters;
-  Buf<lcsf::Ent> d_tab_ent;
-  Buf<int32_t> d_r_inv, d_r_ok, d_status;
-  Buf<uint32_t> d_bitmap;
-  Buf<uint8_t> d_dup;
-  Buf<lc_sf_element> d_out;
-  int64_t *h_small = nullptr;  // pinned: the status words, then the counters
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-};
-
-// lc_append_check: its workspace on the context's first device (grown on
-// demand, freed at lc_close).
-struct ApState {
-  Buf<lc_ap_txn> d_txns;
-  Buf<lc_ap_mop> d_mops;
-  Buf<int64_t> d_values, d_work_off, d_ktab, d_counters, d_count;
-  Buf<int32_t> d_mop_txn, d_rd_mop, d_txn_r0, d_stamp, d_kfirst, d_kflags, d_mop_kslot, d_ord_w, d_mop_flags,
-      d_txn_flags, d_status, d_kslots,
-      d_rt;  // d_rt: 7 arrays of n_txns (launch_real_time's, then rt_lo, rt_hi)
-  Buf<unsigned long long> d_wtab, d_kbest;
-  Buf<uint8_t> d_mop_last, d_nonprefix, d_temp;
-  Buf<lc_ap_edge> d_slots, d_edges_a, d_edges_b;
-  Buf<lc_ap_key> d_keys;
-  int64_t *h_small = nullptr;  // pinned: the status words, the four counts, then the counters
-  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
-};
-
 }  // namespace
 
-struct lc_ctx {
-  std::vector<Dev> devs;
-  // LC_FLAG_WHOLE_GPU: frontier-exchange engines, opened on first use —
-  // single-GPU ones (engine, device) and one over every GPU of the context
-  std::vector<std::pair<lc_fx *, int>> fxs;
-  lc_fx *fx_all = nullptr;
-  bool fx_all_failed = false;
-  std::string err;
-  std::mutex err_mu;
-  lc_stats stats{};
-  // lc_host_register: caller buffers page-locked for this context's devices
-  std::vector<std::pair<const char *, uint64_t>> pinned;
-  std::mutex pin_mu;
-  lc_call_profile prof{};  // lc_last_call_profile
-  EvState evs;             // lc_check_events
-  SfState sfs;             // lc_set_full
-  ApState aps;             // lc_append_check
-};
-
-namespace {
-
-void set_err(lc_ctx *c, const std::string &s) {
+void lcrt::set_err(lc_ctx *c, const std::string &s) {
   std::lock_guard<std::mutex> g(c->err_mu);
   c->err = s;
 }
 
-#define HIP_TRY(ctx, expr)                                                   \
-  do {                                                                       \
-    hipError_t e_ = (expr);                                                  \
-    if (e_ != hipSuccess) {                                                  \
-      set_err(ctx, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-      return -EIO;                                                           \
-    }                                                                        \
-  } while (0)
-
-template <class T>
-int ensure(lc_ctx *c, Buf<T> &b, size_t bytes) {
-  if (b.cap >= bytes && b.p) return 0;
-  if (b.p) (void)hipFree(b.p);
-  b = Buf<T>{};
-  const size_t n = std::max<size_t>(bytes, 256);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.p), n);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    set_err(c, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return -ENOMEM;
-  }
-  b.cap = n;
-  return 0;
-}
+namespace {
 
 // NAME=0 in the environment: a path's switch, read where the path is chosen
 bool env_is_off(const char *name) {
@@ -389,7 +190,6 @@ constexpr int kMaxChunks = 48;
 // MB the runtime's path is the faster one again (a 4.8 MB input staged:
 // 0.07-0.15 ms slower, profiles/r05/stage_ab.txt).
 constexpr size_t kStageMax = size_t(2) << 20;
-inline size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
 // The device's staging buffer (kStageMax bytes, allocated on first use), or
 // null with the context's error set.
 char *stage_buf(lc_ctx *c, Dev &d) {
@@ -458,10 +258,12 @@ int run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off
   return 0;
 }
 
+}  // namespace
+
 // A fused call's lazily copied status (Dev::st_pending): choose the next
 // call's pass from it and return the keys the crash-light decision took (the
 // call's n_gap), or -1 when nothing was pending.
-int64_t settle_status(Dev &d) {
+int64_t lcrt::settle_status(Dev &d) {
   if (!d.st_pending) return -1;
   d.st_pending = false;
   if (hipEventSynchronize(d.es) != hipSuccess) return 0;
@@ -469,6 +271,7 @@ int64_t settle_status(Dev &d) {
   d.use_fused = 4 * (int64_t)n_light > d.st_keys;
   return n_light;
 }
+namespace {
 
 // A call that returned on the completion signal: its pass's HIP-event time,
 // read once the kernel has retired (now, if it has not yet), into the
@@ -533,8 +336,10 @@ void res_ring(Dev &d, const uint64_t (&v)[lcdev::kResWords]) {
     __atomic_store_n(&d.res_h->req[i], lcdev::res_word(v[i], seq), __ATOMIC_RELEASE);
 }
 
+}  // namespace
+
 // Stop the grid (if one is live) and wait for it to leave.
-int res_stop(lc_ctx *c, Dev &d) {
+int lcrt::res_stop(lc_ctx *c, Dev &d) {
   if (!d.res_grid) return 0;
   uint64_t v[lcdev::kResWords] = {};
   v[2] = (uint64_t)lcdev::kResExitKeys;
@@ -543,6 +348,16 @@ int res_stop(lc_ctx *c, Dev &d) {
   HIP_TRY(c, hipStreamSynchronize(d.rst));
   return 0;
 }
+
+int lcrt::side_begin(lc_ctx *c, hipStream_t *st) {
+  Dev &d = c->devs[0];
+  HIP_TRY(c, hipSetDevice(d.id));
+  (void)settle_status(d);
+  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
+  *st = d.stream;
+  return 0;
+}
+namespace {
 
 // One request: returns 0 with every key decided or flagged for the later
 // tiers (d.h_handoff as after fast_tier_kernel), its device time in
@@ -2169,15 +1984,17 @@ int whole_gpu_device(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off, in
   return rc;
 }
 
+}  // namespace
+
 // lc_check_device_ex (48-byte records) and lc_check_device32 (rec32: 24-byte
 // records and key bases), on the context's first device.  `who` names the
 // entry point in its errors.
 // Hot paths: a call without lc_aux outputs or LC_FLAG_WHOLE_GPU issues
 // hipSetDevice and then run_device's calls, nothing else; 24-byte records
 // are decided as they are (Source::ops32) and widened only at a handoff.
-int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const int64_t *d_key_off,
-                 const int64_t *d_key_base, int64_t n_keys, const lc_opts *opts, lc_key_result *d_out,
-                 void *stream, const lc_aux *aux) {
+int lcrt::check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const int64_t *d_key_off,
+                       const int64_t *d_key_base, int64_t n_keys, const lc_opts *opts, lc_key_result *d_out,
+                       void *stream, const lc_aux *aux) {
   const auto t0 = std::chrono::steady_clock::now();
   c->stats = lc_stats{};
   for (Dev &d : c->devs) {
@@ -2257,6 +2074,8 @@ int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const 
                           std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
+
+namespace {
 
 // The argument checks lc_check_frontiers and lc_check_frontiers_counted
 // share (`bad`: the call's own buffer and size test).
@@ -2463,526 +2282,6 @@ int frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64
   return 0;
 }
 
-// lc_set_full: the arrays copied to the context's first device, the element
-// table built, then one mark pass and one element pass per tile (setfull.hip).
-// The duplicates' multiplicities, where the device saw any, the summary and
-// the verdict are the host's (setfull_host.cpp).
-int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_read *reads, int64_t n_reads,
-                    const int64_t *read_values, int64_t n_values, int32_t linearizable, lc_sf_element *out,
-                    lc_sf_summary *sum) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const char *why = nullptr;
-  if (lcsf::check_contract(adds, n_adds, reads, n_reads, read_values, n_values, &why)) {
-    set_err(c, std::string("lc_set_full: ") + why);
-    return -EINVAL;
-  }
-  if (n_adds > 0 && !out) {
-    set_err(c, "lc_set_full: null out");
-    return -EINVAL;
-  }
-  if (n_adds == 0 || n_reads == 0) {  // nothing for the device to do
-    const int rc = lc_set_full_host(adds, n_adds, reads, n_reads, read_values, n_values, linearizable, out, sum);
-    if (rc == -EINVAL) set_err(c, "lc_set_full: two adds of one value");
-    return rc;
-  }
-  SfState &s = c->sfs;
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  (void)settle_status(d);
-  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
-  hipStream_t st = d.stream;
-  constexpr size_t kSmall = 4 + lcsf::kCounterShards * lcsf::kCounterStride;  // in int64
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
-  }
-  lc_sf_limit_info lim;
-  lc_set_full_limits(&lim);
-  const size_t ne = (size_t)n_adds, nr = (size_t)n_reads;
-  const int64_t wpr = (n_reads + 31) / 32;
-  int64_t tile_rows = lim.tile_bytes / (wpr * 4);  // a tile holds at least one row
-  tile_rows = std::max<int64_t>(1, std::min(tile_rows, n_adds));
-  const int64_t n_tiles = (n_adds + tile_rows - 1) / tile_rows;
-  const uint64_t cap = lcsf::table_capacity(n_adds);
-  std::vector<int64_t> work_off(nr + 1);
-  work_off[0] = 0;
-  for (size_t r = 0; r < nr; r++) work_off[r + 1] = work_off[r] + reads[r].len;
-  int e = ensure(c, s.d_adds, sizeof(lc_sf_add) * ne);
-  if (!e) e = ensure(c, s.d_reads, sizeof(lc_sf_read) * nr);
-  if (!e) e = ensure(c, s.d_values, sizeof(int64_t) * (size_t)n_values);
-  if (!e) e = ensure(c, s.d_work_off, sizeof(int64_t) * (nr + 1));
-  if (!e) e = ensure(c, s.d_tab_key, sizeof(int64_t) * cap);
-  if (!e) e = ensure(c, s.d_tab_ent, sizeof(lcsf::Ent) * cap);
-  if (!e) e = ensure(c, s.d_r_inv, sizeof(int32_t) * nr);
-  if (!e) e = ensure(c, s.d_r_ok, sizeof(int32_t) * nr);
-  if (!e) e = ensure(c, s.d_bitmap, sizeof(uint32_t) * (size_t)(tile_rows * wpr));
-  if (!e) e = ensure(c, s.d_dup, ne);
-  if (!e) e = ensure(c, s.d_counters, sizeof(int64_t) * lcsf::kCounterShards * lcsf::kCounterStride);
-  if (!e) e = ensure(c, s.d_status, sizeof(int32_t) * 4);
-  if (!e) e = ensure(c, s.d_out, sizeof(lc_sf_element) * ne);
-  if (e) return e;
-  HIP_TRY(c, hipEventRecord(s.e0, st));
-  HIP_TRY(c, hipMemcpyAsync(s.d_adds.p, adds, sizeof(lc_sf_add) * ne, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(s.d_reads.p, reads, sizeof(lc_sf_read) * nr, hipMemcpyHostToDevice, st));
-  if (n_values)
-    HIP_TRY(c, hipMemcpyAsync(s.d_values.p, read_values, sizeof(int64_t) * (size_t)n_values,
-                              hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(s.d_work_off.p, work_off.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice,
-                            st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
-  // no counter or mark of an earlier call survives
-  HIP_TRY(c, hipMemsetAsync(s.d_counters.p, 0, sizeof(int64_t) * lcsf::kCounterShards * lcsf::kCounterStride, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_status.p, 0, sizeof(int32_t) * 4, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_dup.p, 0, ne, st));
-  lcsf::Ws w{};
-  w.adds = s.d_adds.p;
-  w.reads = s.d_reads.p;
-  w.values = s.d_values.p;
-  w.work_off = s.d_work_off.p;
-  w.n_adds = n_adds;
-  w.n_reads = n_reads;
-  w.n_work = work_off[nr];
-  w.tab_key = s.d_tab_key.p;
-  w.tab_ent = s.d_tab_ent.p;
-  w.cap = cap;
-  w.r_inv = s.d_r_inv.p;
-  w.r_ok = s.d_r_ok.p;
-  w.bitmap = s.d_bitmap.p;
-  w.wpr = wpr;
-  w.dup_seen = s.d_dup.p;
-  w.counters = s.d_counters.p;
-  w.status = s.d_status.p;
-  w.out = s.d_out.p;
-  HIP_TRY(c, lcsf::launch_table(w, st));
-  for (int64_t e0 = 0; e0 < n_adds; e0 += tile_rows)
-    HIP_TRY(c, lcsf::launch_tile(w, e0, std::min(e0 + tile_rows, n_adds), st));
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
-  int64_t *h_counters = s.h_small + 4;
-  HIP_TRY(c, hipMemcpyAsync(h_status, s.d_status.p, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_counters, s.d_counters.p,
-                            sizeof(int64_t) * lcsf::kCounterShards * lcsf::kCounterStride, hipMemcpyDeviceToHost,
-                            st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  if (h_status[0]) {
-    set_err(c, "lc_set_full: two adds of one value (element " + std::to_string(h_status[1]) + " is one)");
-    return -EINVAL;
-  }
-  HIP_TRY(c, hipMemcpyAsync(out, s.d_out.p, sizeof(lc_sf_element) * ne, hipMemcpyDeviceToHost, st));
-  std::vector<uint8_t> marked;
-  if (h_status[2]) {
-    marked.resize(ne);
-    HIP_TRY(c, hipMemcpyAsync(marked.data(), s.d_dup.p, ne, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(c, hipStreamSynchronize(st));
-  // duplicates, exact but not fast: the multiplicities of the marked elements
-  // in one pass over the payload (a history without duplicates never takes it)
-  if (h_status[2])
-    if (int rc = lcsf::count_duplicates(adds, n_adds, reads, n_reads, read_values, marked.data(), out)) return rc;
-  if (sum) {
-    lcsf::summarize(out, n_adds, linearizable, sum);
-    sum->n_phantom = 0;
-    for (int i = 0; i < lcsf::kCounterShards; i++) sum->n_phantom += h_counters[i * lcsf::kCounterStride];
-    sum->n_tiles = n_tiles;
-    float ms = 0;
-    sum->h2d_ms = hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess ? ms : 0;
-    sum->kernel_ms = hipEventElapsedTime(&ms, s.e1, s.e2) == hipSuccess ? ms : 0;
-    sum->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return 0;
-}
-
-// lc_append_check: the arrays copied to the context's first device; rules 1
-// to 6 there (append.hip); the reads the device left open, rule 7 and the
-// summary on the host (append_host.cpp).
-int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
-                  const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
-  const auto t0 = std::chrono::steady_clock::now();
-  lcap::Prep p;
-  const char *why = nullptr;
-  if (lcap::prepare(txns, n_txns, mops, n_mops, values, n_values, out, &p, &why)) {
-    set_err(c, std::string("lc_append_check: ") + why);
-    return -EINVAL;
-  }
-  if (n_txns == 0) return lc_append_check_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
-  const size_t nt = (size_t)n_txns, nm = (size_t)n_mops, nr = p.rd_mop.size();
-  const int64_t n_work = p.work_off[nr];
-  lc_ap_limit_info lim;
-  lc_append_limits(&lim);
-  if (n_values > lim.max_payload || n_work > lim.max_payload) {
-    set_err(c, "lc_append_check: the payload exceeds lc_append_limits' max_payload");
-    return -E2BIG;
-  }
-  if (n_mops > lim.max_mops) {  // (the key table's slot index is an int32)
-    set_err(c, "lc_append_check: more mops than lc_append_limits' max_mops");
-    return -E2BIG;
-  }
-  ApState &s = c->aps;
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  (void)settle_status(d);
-  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
-  hipStream_t st = d.stream;
-  constexpr size_t kCountersLen = lcap::kCounters * lcap::kCounterShards * lcap::kCounterStride;
-  constexpr size_t kSmall = 6 + kCountersLen;  // in int64: 4 status words, 4 counts, the counters
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2, &s.k0, &s.k1, &s.k2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
-  }
-  const uint64_t wcap = lcap::table_capacity(p.n_appends), kcap = lcap::table_capacity(n_mops);
-  const size_t n_slots = 2 * nr + (size_t)n_work, n_edge_room = 2 * nr + (size_t)p.n_appends;
-  const size_t temp_bytes = std::max({lcap::edge_temp_bytes((int64_t)n_slots), lcap::rt_temp_bytes(n_txns),
-                                      lcap::key_temp_bytes(kcap)});
-  int e = ensure(c, s.d_txns, sizeof(lc_ap_txn) * nt);
-  if (!e) e = ensure(c, s.d_mops, sizeof(lc_ap_mop) * nm);
-  if (!e) e = ensure(c, s.d_values, sizeof(int64_t) * (size_t)n_values);
-  if (!e) e = ensure(c, s.d_work_off, sizeof(int64_t) * (nr + 1));
-  if (!e) e = ensure(c, s.d_mop_txn, sizeof(int32_t) * nm);
-  if (!e) e = ensure(c, s.d_rd_mop, sizeof(int32_t) * nr);
-  if (!e) e = ensure(c, s.d_txn_r0, sizeof(int32_t) * (nt + 1));
-  if (!e) e = ensure(c, s.d_wtab, sizeof(unsigned long long) * wcap);
-  if (!e) e = ensure(c, s.d_stamp, sizeof(int32_t) * wcap);
-  if (!e) e = ensure(c, s.d_ktab, sizeof(int64_t) * kcap);
-  if (!e) e = ensure(c, s.d_kbest, sizeof(unsigned long long) * kcap);
-  if (!e) e = ensure(c, s.d_kfirst, sizeof(int32_t) * 3 * kcap);
-  if (!e) e = ensure(c, s.d_kflags, sizeof(int32_t) * kcap);
-  if (!e) e = ensure(c, s.d_mop_kslot, sizeof(int32_t) * nm);
-  if (!e) e = ensure(c, s.d_mop_last, nm);
-  if (!e) e = ensure(c, s.d_ord_w, sizeof(int32_t) * (size_t)n_work);
-  if (!e) e = ensure(c, s.d_nonprefix, nr);
-  if (!e) e = ensure(c, s.d_mop_flags, sizeof(int32_t) * nm);
-  if (!e) e = ensure(c, s.d_txn_flags, sizeof(int32_t) * nt);
-  if (!e) e = ensure(c, s.d_slots, sizeof(lc_ap_edge) * n_slots);
-  // rule 5 bounds the set slots by n_edge_room: the wr / rw slots are two per read, and a ww slot is
-  // set only inside an order without repeats and phantoms, whose entries are distinct appends of its key
-  if (!e) e = ensure(c, s.d_edges_a, sizeof(lc_ap_edge) * n_edge_room);
-  if (!e) e = ensure(c, s.d_edges_b, sizeof(lc_ap_edge) * n_edge_room);
-  if (!e) e = ensure(c, s.d_kslots, sizeof(int32_t) * kcap);
-  if (!e) e = ensure(c, s.d_keys, sizeof(lc_ap_key) * nm);
-  if (!e) e = ensure(c, s.d_counters, sizeof(int64_t) * kCountersLen);
-  if (!e) e = ensure(c, s.d_count, sizeof(int64_t) * 4);
-  if (!e) e = ensure(c, s.d_status, sizeof(int32_t) * 4);
-  if (!e) e = ensure(c, s.d_rt, sizeof(int32_t) * 7 * nt);
-  if (!e) e = ensure(c, s.d_temp, temp_bytes);
-  if (e) return e;
-  HIP_TRY(c, hipEventRecord(s.e0, st));
-  HIP_TRY(c, hipMemcpyAsync(s.d_txns.p, txns, sizeof(lc_ap_txn) * nt, hipMemcpyHostToDevice, st));
-  if (nm) {
-    HIP_TRY(c, hipMemcpyAsync(s.d_mops.p, mops, sizeof(lc_ap_mop) * nm, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(s.d_mop_txn.p, p.mop_txn.data(), sizeof(int32_t) * nm, hipMemcpyHostToDevice, st));
-  }
-  if (n_values)
-    HIP_TRY(c, hipMemcpyAsync(s.d_values.p, values, sizeof(int64_t) * (size_t)n_values, hipMemcpyHostToDevice, st));
-  if (nr) HIP_TRY(c, hipMemcpyAsync(s.d_rd_mop.p, p.rd_mop.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(s.d_txn_r0.p, p.txn_r0.data(), sizeof(int32_t) * (nt + 1), hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(s.d_work_off.p, p.work_off.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice,
-                            st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
-  // nothing of an earlier call survives: empty tables (every empty word is
-  // all ones), no flags, no edge slots, no counts
-  HIP_TRY(c, hipMemsetAsync(s.d_wtab.p, 0xFF, sizeof(unsigned long long) * wcap, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_stamp.p, 0xFF, sizeof(int32_t) * wcap, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_ktab.p, 0xFF, sizeof(int64_t) * kcap, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_kbest.p, 0, sizeof(unsigned long long) * kcap, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_kfirst.p, 0xFF, sizeof(int32_t) * 3 * kcap, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_kflags.p, 0, sizeof(int32_t) * kcap, st));
-  if (nm) HIP_TRY(c, hipMemsetAsync(s.d_mop_flags.p, 0, sizeof(int32_t) * nm, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_txn_flags.p, 0, sizeof(int32_t) * nt, st));  // (no kernel writes them without mops)
-  if (nm) HIP_TRY(c, hipMemsetAsync(s.d_mop_last.p, 0, nm, st));
-  if (nr) HIP_TRY(c, hipMemsetAsync(s.d_nonprefix.p, 0, nr, st));
-  if (n_slots) HIP_TRY(c, hipMemsetAsync(s.d_slots.p, 0xFF, sizeof(lc_ap_edge) * n_slots, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_counters.p, 0, sizeof(int64_t) * kCountersLen, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_count.p, 0, sizeof(int64_t) * 4, st));
-  HIP_TRY(c, hipMemsetAsync(s.d_status.p, 0, sizeof(int32_t) * 4, st));
-  lcap::Ws w{};
-  w.txns = s.d_txns.p;
-  w.mops = s.d_mops.p;
-  w.values = s.d_values.p;
-  w.mop_txn = s.d_mop_txn.p;
-  w.rd_mop = s.d_rd_mop.p;
-  w.txn_r0 = s.d_txn_r0.p;
-  w.work_off = s.d_work_off.p;
-  w.n_txns = n_txns;
-  w.n_mops = n_mops;
-  w.n_real = (int64_t)nr;
-  w.n_work = n_work;
-  w.wtab = s.d_wtab.p;
-  w.stamp = s.d_stamp.p;
-  w.wcap = wcap;
-  w.ktab = s.d_ktab.p;
-  w.kbest = s.d_kbest.p;
-  w.kfirst = s.d_kfirst.p;
-  w.kflags = s.d_kflags.p;
-  w.kcap = kcap;
-  w.mop_kslot = s.d_mop_kslot.p;
-  w.mop_last = s.d_mop_last.p;
-  w.ord_w = s.d_ord_w.p;
-  w.nonprefix = s.d_nonprefix.p;
-  w.mop_flags = s.d_mop_flags.p;
-  w.txn_flags = s.d_txn_flags.p;
-  w.slots = s.d_slots.p;
-  w.keys = s.d_keys.p;
-  w.counters = s.d_counters.p;
-  w.status = s.d_status.p;
-  int32_t *rt = s.d_rt.p;  // ok_idx, ok_comp, byc, comp_sorted, pm, rt_lo, rt_hi
-  int32_t *d_byc = rt + 2 * nt, *d_lo = rt + 5 * nt, *d_hi = rt + 6 * nt;
-  HIP_TRY(c, hipEventRecord(s.k0, st));
-  if (nm) HIP_TRY(c, lcap::launch_rules(w, s.d_kslots.p, s.d_count.p + 3, s.d_temp.p, temp_bytes, st));
-  if (n_slots) HIP_TRY(c, lcap::launch_edge_select(w, s.d_edges_a.p, s.d_count.p, s.d_temp.p, temp_bytes, st));
-  HIP_TRY(c, lcap::launch_real_time(w, p.n_ok, rt, rt + nt, d_byc, rt + 3 * nt, rt + 4 * nt, d_lo, d_hi,
-                                    s.d_count.p + 2, s.d_temp.p, temp_bytes, st));
-  HIP_TRY(c, hipEventRecord(s.k1, st));
-  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
-  int64_t *h_count = s.h_small + 2, *h_counters = s.h_small + 6;  // counts: set slots, edges, (OK txns), keys
-  HIP_TRY(c, hipMemcpyAsync(h_status, s.d_status.p, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_count, s.d_count.p, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_counters, s.d_counters.p, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  if (h_status[0]) {
-    set_err(c, "lc_append_check: two appends of one (key, element) (mop " + std::to_string(h_status[1]) + " is one)");
-    return -EINVAL;
-  }
-  const int64_t n_sel = h_count[0], n_keys = h_count[3];
-  if (n_sel > (int64_t)n_edge_room || n_keys > n_mops) {  // (more edges than rule 5 allows: a bug, not an input)
-    set_err(c, "lc_append_check: inconsistent edge or key count");
-    return -EIO;
-  }
-  h_count[1] = 0;
-  HIP_TRY(c, hipEventRecord(s.k2, st));
-  if (n_sel > 0) {
-    HIP_TRY(c, lcap::launch_edge_sort(s.d_edges_a.p, s.d_edges_b.p, n_sel, s.d_count.p + 1, s.d_temp.p, temp_bytes,
-                                      st));
-  }
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  if (n_sel > 0) HIP_TRY(c, hipMemcpyAsync(h_count + 1, s.d_count.p + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  if (nm) HIP_TRY(c, hipMemcpyAsync(out->mop_flags, s.d_mop_flags.p, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->txn_flags, s.d_txn_flags.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-  if (n_keys)
-    HIP_TRY(c, hipMemcpyAsync(out->keys, s.d_keys.p, sizeof(lc_ap_key) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
-  if (p.n_ok) HIP_TRY(c, hipMemcpyAsync(out->byc, d_byc, sizeof(int32_t) * (size_t)p.n_ok, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->rt_lo, d_lo, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->rt_hi, d_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  const int64_t n_edges = h_count[1];
-  if (n_edges > 0) {  // only the unique edges reach the caller
-    HIP_TRY(c, hipMemcpyAsync(out->edges, s.d_edges_a.p, sizeof(lc_ap_edge) * (size_t)n_edges, hipMemcpyDeviceToHost,
-                              st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-  }
-  // the key records: ascending by key; first_dup of an order with two
-  // phantoms from its definition (the device sees repeats of written elements)
-  std::sort(out->keys, out->keys + n_keys, [](const lc_ap_key &a, const lc_ap_key &b) { return a.key < b.key; });
-  for (int64_t k = 0; k < n_keys; k++) {
-    lc_ap_key &kr = out->keys[k];
-    if (!(kr.flags & lcap::kKeyTwoPhantoms)) continue;
-    kr.flags &= ~lcap::kKeyTwoPhantoms;
-    kr.first_dup = lcap::first_dup_direct(values + mops[kr.longest].value, kr.len);
-  }
-  // exact but not fast: the txns the device left open (a history without
-  // non-prefix reads and twice-phantom orders has none)
-  int64_t counts[lcap::kCounters] = {0}, n_nonprefix = 0;
-  for (int b = 0; b < lcap::kCounters; b++)
-    for (int i = 0; i < lcap::kCounterShards; i++)
-      counts[b] += h_counters[((size_t)b * lcap::kCounterShards + i) * lcap::kCounterStride];
-  const int64_t n_slow = counts[5];
-  if (n_slow) {
-    lcap::Writers wr;
-    if (wr.build(txns, n_txns, mops, n_mops)) {
-      set_err(c, "lc_append_check: the host found two appends of one pair where the device found none");
-      return -EIO;
-    }
-    for (int64_t t = 0; t < n_txns; t++) {
-      if (!(out->txn_flags[t] & lcap::kTxnSlow)) continue;
-      lcap::rules34_direct(txns, mops, values, p, wr, t, out->mop_flags, out->txn_flags);
-      for (int64_t m = txns[t].mop_off; m < txns[t].mop_off + txns[t].mop_len; m++) {
-        n_nonprefix += out->mop_flags[m] & LC_AP_R_NONPREFIX;
-        for (int b = 0; b < 5; b++) counts[b] += (out->mop_flags[m] >> (b + 1)) & 1;
-      }
-    }
-  }
-  lc_ap_summary sm;
-  lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm);
-  sm.n_slow_reads = n_slow;
-  float ms = 0;
-  sm.h2d_ms = hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess ? ms : 0;
-  sm.kernel_ms = hipEventElapsedTime(&ms, s.k0, s.k1) == hipSuccess ? ms : 0;
-  if (hipEventElapsedTime(&ms, s.k2, s.e2) == hipSuccess) sm.kernel_ms += ms;
-  sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (sum) *sum = sm;
-  return 0;
-}
-
-// lc_events_pack / lc_check_events: the events copied to the context's first
-// device and split, completed and packed there (events.hip).  On return the
-// stream has drained, s.h_status holds the call's counts, and the records
-// are in s.d_ops32 / d_completion / d_key_off / d_key_base.
-int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_events, int64_t n_keys) {
-  const std::string name(who);
-  EvState &s = c->evs;
-  s.stats = lc_events_stats{};
-  if (n_events < 0 || n_keys < 0 || (n_events > 0 && !ev)) {
-    set_err(c, name + ": null events or a negative count");
-    return -EINVAL;
-  }
-  if (n_events >= (int64_t(1) << 31) || n_keys >= (int64_t(1) << 31)) {
-    set_err(c, name + ": 2^31 or more events or keys");
-    return -EINVAL;
-  }
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  (void)settle_status(d);
-  if (int e = res_stop(c, d)) return e;  // the resident grid leaves before other work runs
-  hipStream_t st = d.stream;
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_status), sizeof(lcev::Status), 0));
-  }
-  const size_t n = (size_t)n_events, k = (size_t)n_keys;
-  int e = ensure(c, s.d_ev, sizeof(lc_event) * n);
-  if (!e) e = ensure(c, s.d_cnt, sizeof(int32_t) * k);
-  if (!e) e = ensure(c, s.d_cursor, sizeof(int32_t) * k);
-  if (!e) e = ensure(c, s.d_seg_off, sizeof(int64_t) * (k + 1));
-  if (!e) e = ensure(c, s.d_seg, sizeof(uint32_t) * n);
-  if (!e) e = ensure(c, s.d_match, sizeof(int32_t) * n);
-  if (!e) e = ensure(c, s.d_gtab, 2 * sizeof(unsigned long long) * n);
-  if (!e) e = ensure(c, s.d_nops, sizeof(int32_t) * k);
-  if (!e) e = ensure(c, s.d_nfail, sizeof(int32_t) * k);
-  if (!e) e = ensure(c, s.d_nign, sizeof(int32_t) * k);
-  if (!e) e = ensure(c, s.d_key_off, sizeof(int64_t) * (k + 1));
-  if (!e) e = ensure(c, s.d_key_base, sizeof(int64_t) * k);
-  if (!e) e = ensure(c, s.d_ops32, sizeof(lc_op32) * n);
-  if (!e) e = ensure(c, s.d_completion, sizeof(int32_t) * n);
-  if (!e) e = ensure(c, s.d_status, sizeof(lcev::Status));
-  if (e) return e;
-  HIP_TRY(c, hipEventRecord(s.e0, st));
-  if (n) HIP_TRY(c, hipMemcpyAsync(s.d_ev.p, ev, sizeof(lc_event) * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
-  // no counter of an earlier call, larger or smaller, survives
-  HIP_TRY(c, hipMemsetAsync(s.d_status.p, 0, sizeof(lcev::Status), st));
-  if (k > 1) {
-    HIP_TRY(c, hipMemsetAsync(s.d_cnt.p, 0, sizeof(int32_t) * k, st));
-    HIP_TRY(c, hipMemsetAsync(s.d_cursor.p, 0, sizeof(int32_t) * k, st));
-  }
-  lcev::Ws w{};
-  w.ev = s.d_ev.p;
-  w.n = n_events;
-  w.k = n_keys;
-  w.cnt = s.d_cnt.p;
-  w.cursor = s.d_cursor.p;
-  w.seg_off = s.d_seg_off.p;
-  w.seg = s.d_seg.p;
-  w.match = s.d_match.p;
-  w.gtab = s.d_gtab.p;
-  w.nops = s.d_nops.p;
-  w.nfail = s.d_nfail.p;
-  w.nign = s.d_nign.p;
-  w.key_off = s.d_key_off.p;
-  w.key_base = s.d_key_base.p;
-  w.ops32 = s.d_ops32.p;
-  w.completion = s.d_completion.p;
-  w.status = s.d_status.p;
-  HIP_TRY(c, lcev::launch_events(w, st));
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  HIP_TRY(c, hipMemcpyAsync(s.h_status, s.d_status.p, sizeof(lcev::Status), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) s.stats.h2d_ms = ms;
-  if (hipEventElapsedTime(&ms, s.e1, s.e2) == hipSuccess) s.stats.split_ms = ms;
-  const lcev::Status &h = *s.h_status;
-  s.stats.n_events = n_events;
-  s.stats.n_client = h.n_client;
-  s.stats.n_ops = h.n_ops;
-  s.stats.n_fail_pairs = h.n_fail;
-  s.stats.n_ignored_completions = h.n_ignored;
-  s.stats.n_big_keys = h.n_big;
-  if (h.err) {
-    set_err(c, name + ": an event with a key outside [-1, n_keys) or a type above 3 (the last one at position " +
-                   std::to_string(h.err_pos) + ")");
-    return -EINVAL;
-  }
-  return 0;
-}
-
-// The packed records of the last events_device call into the caller's arrays.
-int events_copy_out(lc_ctx *c, const char *who, int64_t n_keys, lc_events_out *out) {
-  EvState &s = c->evs;
-  const lcev::Status &h = *s.h_status;
-  if (!out->key_off || (n_keys > 0 && !out->key_base) || out->cap < h.n_invoke ||
-      (h.n_ops > 0 && (!out->ops32 || !out->completion))) {
-    set_err(c, std::string(who) + ": lc_events_out: a null array, or cap below the number of invokes");
-    return -EINVAL;
-  }
-  hipStream_t st = c->devs[0].stream;
-  const size_t k = (size_t)n_keys, m = (size_t)h.n_ops;
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(out->ops32, s.d_ops32.p, sizeof(lc_op32) * m, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(out->completion, s.d_completion.p, sizeof(int32_t) * m,
-                              hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(c, hipMemcpyAsync(out->key_off, s.d_key_off.p, sizeof(int64_t) * (k + 1), hipMemcpyDeviceToHost,
-                            st));
-  if (k)
-    HIP_TRY(c, hipMemcpyAsync(out->key_base, s.d_key_base.p, sizeof(int64_t) * k, hipMemcpyDeviceToHost,
-                              st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  out->n_ops = h.n_ops;
-  return 0;
-}
-
-// lc_check_events after events_device: the records, resident, through
-// lc_check_device32's path; results and lc_aux outputs copied to the host.
-int events_check(lc_ctx *c, int64_t n_keys, const lc_opts *opts, lc_key_result *out, const lc_aux *aux) {
-  EvState &s = c->evs;
-  Dev &d = c->devs[0];
-  if (n_keys == 0) return 0;
-  if (!out) {
-    set_err(c, "lc_check_events: null out");
-    return -EINVAL;
-  }
-  const size_t k = (size_t)n_keys, m = (size_t)s.h_status->n_ops;
-  const bool want_wit = aux && aux->witness && aux->witness_kind;
-  const bool want_cert = aux && aux->certificate;
-  if (aux && (aux->witness || aux->certificate) && !(aux->witness && aux->witness_kind)) {
-    set_err(c, "lc_check_events: lc_aux needs witness and witness_kind");
-    return -EINVAL;
-  }
-  int e = ensure(c, s.d_res, sizeof(lc_key_result) * k);
-  if (!e && want_wit) e = ensure(c, d.d_wit, sizeof(int32_t) * m);
-  if (!e && want_wit) e = ensure(c, d.d_kind, sizeof(int32_t) * k);
-  if (!e && want_cert) e = ensure(c, d.d_cert, 4 * sizeof(int32_t) * k);
-  if (!e && want_cert) e = ensure(c, d.d_cset, sizeof(int32_t) * m);
-  if (e) return e;
-  lc_aux dev_aux{};
-  if (want_wit) {
-    dev_aux.witness = d.d_wit.p;
-    dev_aux.witness_kind = d.d_kind.p;
-  }
-  if (want_cert) {
-    dev_aux.certificate = d.d_cert.p;
-    dev_aux.certificate_set = d.d_cset.p;
-  }
-  e = check_device(c, "lc_check_events", s.d_ops32.p, true, s.d_key_off.p, s.d_key_base.p, n_keys, opts,
-                   s.d_res.p, nullptr, want_wit ? &dev_aux : nullptr);
-  if (e) return e;
-  hipStream_t st = d.stream;
-  HIP_TRY(c, hipMemcpyAsync(out, s.d_res.p, sizeof(lc_key_result) * k, hipMemcpyDeviceToHost, st));
-  if (want_wit) {
-    if (m)
-      HIP_TRY(c, hipMemcpyAsync(aux->witness, d.d_wit.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(aux->witness_kind, d.d_kind.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost,
-                              st));
-  }
-  if (want_cert) {
-    HIP_TRY(c, hipMemcpyAsync(aux->certificate, d.d_cert.p, 4 * sizeof(int32_t) * k,
-                              hipMemcpyDeviceToHost, st));
-    if (m && aux->certificate_set)
-      HIP_TRY(c, hipMemcpyAsync(aux->certificate_set, d.d_cset.p, sizeof(int32_t) * m,
-                                hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(c, hipStreamSynchronize(st));
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -3056,38 +2355,12 @@ int lc_open(uint32_t device_mask, lc_ctx **out) {
 void lc_close(lc_ctx *c) {
   if (!c) return;
   if (!c->devs.empty()) {
-    EvState &s = c->evs;
+    // the side checkers' states live on the first device
     (void)hipSetDevice(c->devs[0].id);
     if (c->devs[0].stream) (void)hipStreamSynchronize(c->devs[0].stream);
-    // every Buf of EvState
-    for (void *b : std::initializer_list<void *>{
-             s.d_ev.p, s.d_cnt.p, s.d_cursor.p, s.d_match.p, s.d_nops.p, s.d_nfail.p, s.d_nign.p,
-             s.d_completion.p, s.d_seg_off.p, s.d_key_off.p, s.d_key_base.p, s.d_seg.p, s.d_gtab.p,
-             s.d_ops32.p, s.d_res.p, s.d_status.p})
-      if (b) (void)hipFree(b);
-    if (s.h_status) (void)hipHostFree(s.h_status);
-    for (hipEvent_t e : {s.e0, s.e1, s.e2})
-      if (e) (void)hipEventDestroy(e);
-    // every Buf of SfState
-    SfState &f = c->sfs;
-    for (void *b : std::initializer_list<void *>{
-             f.d_adds.p, f.d_reads.p, f.d_values.p, f.d_work_off.p, f.d_tab_key.p, f.d_counters.p,
-             f.d_tab_ent.p, f.d_r_inv.p, f.d_r_ok.p, f.d_status.p, f.d_bitmap.p, f.d_dup.p, f.d_out.p})
-      if (b) (void)hipFree(b);
-    if (f.h_small) (void)hipHostFree(f.h_small);
-    for (hipEvent_t e : {f.e0, f.e1, f.e2})
-      if (e) (void)hipEventDestroy(e);
-    // every Buf of ApState
-    ApState &a = c->aps;
-    for (void *b : std::initializer_list<void *>{
-             a.d_txns.p, a.d_mops.p, a.d_values.p, a.d_work_off.p, a.d_ktab.p, a.d_counters.p, a.d_count.p,
-             a.d_mop_txn.p, a.d_rd_mop.p, a.d_txn_r0.p, a.d_stamp.p, a.d_kfirst.p, a.d_kflags.p, a.d_mop_kslot.p,
-             a.d_ord_w.p, a.d_mop_flags.p, a.d_txn_flags.p, a.d_status.p, a.d_kslots.p, a.d_rt.p, a.d_wtab.p, a.d_kbest.p,
-             a.d_mop_last.p, a.d_nonprefix.p, a.d_temp.p, a.d_slots.p, a.d_edges_a.p, a.d_edges_b.p, a.d_keys.p})
-      if (b) (void)hipFree(b);
-    if (a.h_small) (void)hipHostFree(a.h_small);
-    for (hipEvent_t e : {a.e0, a.e1, a.e2, a.k0, a.k1, a.k2})
-      if (e) (void)hipEventDestroy(e);
+    release(c->evs);
+    release(c->sfs);
+    release(c->aps);
   }
   for (auto &f : c->fxs) lc_fx_close(f.first);
   if (c->fx_all) lc_fx_close(c->fx_all);
@@ -3474,65 +2747,6 @@ int lc_check_frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_o
     set_err(c, "lc_check_frontiers_counted: out of host memory");
     return -ENOMEM;
   }
-}
-
-int lc_events_pack(lc_ctx *c, const lc_event *ev, int64_t n_events, int64_t n_keys, lc_events_out *out) {
-  if (!c) return -EINVAL;
-  const auto t0 = std::chrono::steady_clock::now();
-  if (!out) {
-    set_err(c, "lc_events_pack: null out");
-    return -EINVAL;
-  }
-  int rc = events_device(c, "lc_events_pack", ev, n_events, n_keys);
-  if (!rc) rc = events_copy_out(c, "lc_events_pack", n_keys, out);
-  c->evs.stats.total_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
-int lc_check_events(lc_ctx *c, const lc_event *ev, int64_t n_events, int64_t n_keys, const lc_opts *opts,
-                    lc_key_result *out, const lc_aux *aux, lc_events_out *packed) {
-  if (!c) return -EINVAL;
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms = [&] {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  };
-  int rc = events_device(c, "lc_check_events", ev, n_events, n_keys);
-  if (!rc && packed) rc = events_copy_out(c, "lc_check_events", n_keys, packed);
-  const double t1 = ms();
-  if (!rc) rc = events_check(c, n_keys, opts, out, aux);
-  c->evs.stats.check_ms = ms() - t1;
-  c->evs.stats.total_ms = ms();
-  return rc;
-}
-
-int lc_set_full(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_read *reads, int64_t n_reads,
-                const int64_t *read_values, int64_t n_values, int32_t linearizable, lc_sf_element *out,
-                lc_sf_summary *sum) {
-  if (!c) return -EINVAL;
-  try {
-    return set_full_device(c, adds, n_adds, reads, n_reads, read_values, n_values, linearizable, out, sum);
-  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
-    set_err(c, "lc_set_full: out of host memory");
-    return -ENOMEM;
-  }
-}
-
-int lc_append_check(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
-                    const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
-  if (!c) return -EINVAL;
-  try {
-    return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum);
-  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
-    set_err(c, "lc_append_check: out of host memory");
-    return -ENOMEM;
-  }
-}
-
-int lc_last_events_stats(lc_ctx *c, lc_events_stats *out) {
-  if (!c || !out) return -EINVAL;
-  *out = c->evs.stats;
-  return 0;
 }
 
 int lc_pack32(const lc_op *ops, const int64_t *key_off, int64_t n_keys, lc_op32 *out,

@@ -1,0 +1,235 @@
+// runtime.h — what lincheck.cpp (the register path; it defines the functions
+// declared here) shares with the side checkers' drivers (*_dev.cpp).  Internal:
+// not installed with include/, and lcrt has hidden visibility.
+#pragma once
+#include <errno.h>
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../../include/lincheck.h"
+#include "../../../include/lincheck_fx.h"
+#include "kernels.h"
+#include "counted.h"
+#include "events.h"
+#include "workspace.h"
+
+namespace lcrt __attribute__((visibility("hidden"))) {
+
+// A device buffer with its capacity in bytes (ensure(): at least 256 bytes,
+// grow-only, freed at lc_close).  No destructor: lc_open copies a Dev into
+// lc_ctx::devs, and lc_close frees every buffer once.
+template <class T>
+struct Buf {
+  T *p = nullptr;
+  size_t cap = 0;
+};
+
+struct Dev {
+  int id = -1;
+  hipStream_t stream = nullptr;
+
+  // ---- device buffers (each is named once more, in lc_close's list) ----
+  Buf<lc_op> d_ops;
+  Buf<int64_t> d_off;
+  Buf<lc_key_result> d_out;
+  Buf<int32_t> d_ovf, d_ovf2;
+  Buf<int32_t> d_jit;
+  Buf<int32_t> d_flags;         // per key: handed over by the fast tier (zero between calls)
+  Buf<int32_t> d_jit2;          // keys the gap tier passes on
+  Buf<int32_t> d_gap2;          // keys the crash-light pass leaves to the gap tier
+  Buf<int32_t> d_gws;           // gap-tier workspace
+  Buf<char> d_cex;              // gap-tier counterexample intervals + probes
+  Buf<void> d_ws;               // HBM tiers' workspace
+  Buf<int32_t> d_wit, d_kind;   // lc_check_ex: device copies of the lc_aux outputs
+  Buf<int32_t> d_cert, d_cset;  // lc_aux certificates (4 per key), their position sets
+  Buf<int32_t> d_cws;           // certificate workspace
+  Buf<char> d_ops32;            // copy pipeline: lc_check32 / lc_check16's staging records
+  Buf<int64_t> d_base;          // ... and the keys' bases
+  Buf<lcdev::WitnessStatus> d_wst;  // LC_FLAG_SEARCH_WITNESS: the stage's status words
+
+  // ---- events ----
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  hipEvent_t ef = nullptr;                  // after the first pass
+  hipEvent_t el = nullptr;                  // after the crash-light pass
+  hipEvent_t eg = nullptr;                  // after the gap tier
+  hipEvent_t eh0 = nullptr, eh1 = nullptr;  // around lc_check's host-to-device copies
+
+  // ---- status words, and what the next call has to know about them ----
+  lcdev::KStatus *d_status = nullptr;   // all-zero between calls
+  lcdev::KStatus *h_status = nullptr;   // pinned: D2H copies of d_status
+  int32_t *h_handoff = nullptr;         // host-coherent: [0] fast tier handed keys over, [1] a fused
+                                        // pass's crash-light key count (status_settle_kernel)
+  int32_t *h_handoff_dev = nullptr;     // its device address
+  bool status_dirty = true;             // d_status may be non-zero
+  // the handoff flags may be non-zero (the fast tier raised some and no
+  // compaction, which clears them, followed)
+  bool flags_dirty = true;
+  // A fused call that handed nothing over copies its status without waiting
+  // for it (the counts only choose the next call's pass and fill this call's
+  // n_gap_keys): the next call, or lc_last_stats, settles it (settle_status).
+  hipEvent_t es = nullptr;
+  bool st_pending = false;
+  int64_t st_keys = 0;
+  bool use_fused = false;  // the next call takes the fused version-order + crash-light pass
+  // some key of the last run_device call may be LC_INVALID (a key was handed
+  // over past the version-order tier, which decides valid keys only): the
+  // certificate pass runs only then
+  bool maybe_invalid = true;
+
+  // ---- completion signal ----
+  // The version-order / fused pass's follower signal (kernels.h
+  // launch_done_signal): a host-mapped word the host spins on instead of
+  // waiting for an event; the pass's HIP-event time is read later
+  // (timing_pending)
+  uint32_t *h_done = nullptr, *h_done_dev = nullptr;
+  uint32_t seq = 0;
+  bool timing_pending = false;
+
+  // ---- resident grid ----
+  // the resident version-order grid (kernels.h launch_fast_resident), on its
+  // own stream; res_grid: workgroups of the live grid (0: none)
+  lcdev::ResHost *res_h = nullptr, *res_h_dev = nullptr;
+  lcdev::ResDev *res_d = nullptr;
+  hipStream_t rst = nullptr;
+  int64_t res_grid = 0;
+  uint32_t res_seq = 0;
+  int res_khz = 0;          // the device's wall-clock rate
+  int64_t res_idle_us = 50; // LC_RESIDENT_IDLE_US (read at each grid launch)
+  int64_t res_cap = -1;     // lcdev::fast_resident_capacity() (once)
+  bool res_broken = false;  // a request the grid did not complete: launches only from then on
+
+  // ---- copy pipeline ----
+  // lc_check's host-to-device pipeline: the copy streams and one event per
+  // chunk (its records landed); the staging records are d_ops32 / d_base
+  // (two copy streams, chunks alternating: two DMA engines read host memory
+  // at once; measured 52-53 GB/s with one, 57 GB/s with two on one GPU)
+  hipStream_t cst = nullptr, cst2 = nullptr;
+  std::vector<hipEvent_t> cev;
+  // lc_check's small calls from pageable memory: inputs and outputs pass
+  // through this pinned buffer (kStageMax)
+  char *h_stage = nullptr;
+
+  // ---- statistics ----
+  double kernel_ms = 0, fast_ms = 0, gap_ms = 0, jit_ms = 0, hbm_ms = 0;
+  int64_t n_gap = 0, n_jit = 0, n_hbm = 0;
+  int malformed = 0;
+  lc_counted_stats counted{};               // this device's share of lc_last_counted_stats
+  lc_witness_stats wit{};                   // this device's share of lc_last_witness_stats
+  lc_counted_witness_stats cwit{};          // this device's share of lc_last_counted_witness_stats
+  lc_device_stats last{};                   // this device's share of the last lc_check
+  double t_start = 0, t_end = 0;            // lc_call_profile: this thread's span (ms since the call began)
+  // this device's share of lc_last_totals: written only by the device's own
+  // thread during a call (check_host runs one per device), summed by
+  // lc_last_totals after the threads are joined
+  lc_totals tot{};
+};
+
+// The side checkers' states: one grow-only arena each on the context's first
+// device, carved into the call's arrays (workspace.h); events and pinned words
+// made by the first call; release() frees everything (lc_close).  No device
+// pointer outlives a call but through EvState::w.
+
+// lc_check_events / lc_events_pack.  w: the last events_device call's arrays;
+// events_copy_out and events_check read the packed records through it, so
+// nothing grows the arena in between.
+struct EvState {
+  Buf<char> arena;
+  Buf<lc_key_result> d_res;          // events_check's results
+  lcev::Ws w{};
+  lcev::Status *h_status = nullptr;  // pinned
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  lc_events_stats stats{};
+};
+
+struct SfState {  // lc_set_full
+  Buf<char> arena;
+  int64_t *h_small = nullptr;  // pinned: the status words, then the counters
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+};
+
+struct ApState {  // lc_append_check
+  Buf<char> arena;
+  int64_t *h_small = nullptr;  // pinned: the status words, the four counts, then the counters
+  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
+};
+
+void release(EvState &s);
+void release(SfState &s);
+void release(ApState &s);
+
+void set_err(lc_ctx *c, const std::string &s);
+
+#define HIP_TRY(ctx, expr)                                                   \
+  do {                                                                       \
+    hipError_t e_ = (expr);                                                  \
+    if (e_ != hipSuccess) {                                                  \
+      lcrt::set_err(ctx, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+      return -EIO;                                                           \
+    }                                                                        \
+  } while (0)
+
+template <class T>
+int ensure(lc_ctx *c, Buf<T> &b, size_t bytes) {
+  if (b.cap >= bytes && b.p) return 0;
+  if (b.p) (void)hipFree(b.p);
+  b = Buf<T>{};
+  const size_t n = bytes > 256 ? bytes : 256;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.p), n);
+  if (e != hipSuccess) {
+    b.p = nullptr;
+    set_err(c, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return -ENOMEM;
+  }
+  b.cap = n;
+  return 0;
+}
+
+int64_t settle_status(Dev &d);
+int res_stop(lc_ctx *c, Dev &d);
+int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const int64_t *d_key_off,
+                 const int64_t *d_key_base, int64_t n_keys, const lc_opts *opts, lc_key_result *d_out,
+                 void *stream, const lc_aux *aux);
+
+// How a side checker's call begins: the context's first device selected, a
+// pending status settled, the resident grid gone (it leaves before other
+// work runs).  *st is that device's stream.
+int side_begin(lc_ctx *c, hipStream_t *st);
+
+// An input's device copy, which the kernels only read (const in their Ws), as
+// the destination of the host's copy.
+template <class T>
+inline T *writable(const T *p) {
+  return const_cast<T *>(p);
+}
+
+// The time between two recorded events that have completed, or 0.
+inline float elapsed_ms(hipEvent_t a, hipEvent_t b) {
+  float ms = 0;
+  return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0;
+}
+
+}  // namespace lcrt
+
+struct lc_ctx {
+  std::vector<lcrt::Dev> devs;
+  // LC_FLAG_WHOLE_GPU: frontier-exchange engines, opened on first use —
+  // single-GPU ones (engine, device) and one over every GPU of the context
+  std::vector<std::pair<lc_fx *, int>> fxs;
+  lc_fx *fx_all = nullptr;
+  bool fx_all_failed = false;
+  std::string err;
+  std::mutex err_mu;
+  lc_stats stats{};
+  // lc_host_register: caller buffers page-locked for this context's devices
+  std::vector<std::pair<const char *, uint64_t>> pinned;
+  std::mutex pin_mu;
+  lc_call_profile prof{};  // lc_last_call_profile
+  lcrt::EvState evs;       // lc_check_events
+  lcrt::SfState sfs;       // lc_set_full
+  lcrt::ApState aps;       // lc_append_check
+};

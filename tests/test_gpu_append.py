@@ -276,6 +276,28 @@ def test_workspace_reuse(ctx):
     for what, arrays in (("small", small), ("large", large), ("small again", small),
                          ("anomalous", (bad.txns, bad.mops, bad.values)), ("large again", large)):
         _agree(ctx, *arrays, what=what)
+    # the mix of sizes flips while the total stays about the same: many txns on
+    # two keys with a short read now and then (of its own key while that is
+    # short, later of a key nobody appends to), against few txns on many keys
+    # whose reads are long.  On a fresh context the per-txn arrays shrink and
+    # the per-item arrays grow, so every array moves inside a workspace that
+    # does not grow, and back.
+    lists = {0: [], 1: []}
+    many_txns = []
+    for i in range(400):
+        lists[i % 2].append(i + 1)
+        read = ("r", i % 2, list(lists[i % 2])) if i < 24 else ("r", 2, [])
+        many_txns.append([("a", i % 2, i + 1)] + [read] * (i % 8 == 7))
+    long_reads = []
+    for k in range(30):
+        elems = [1000 + 8 * k + j for j in range(8)]
+        long_reads += [[("a", k, e) for e in elems], [("r", k, elems)], [("r", k, elems)]]
+    many_txns, long_reads = serial(many_txns), serial(long_reads)
+    assert len(many_txns[0]) > 4 * len(long_reads[0]) and 3 * len(many_txns[2]) < len(long_reads[2])
+    with abi.Context(device_mask=1) as c:
+        for what, arrays in (("many txns", many_txns), ("long reads", long_reads), ("many txns again", many_txns)):
+            _, gs = _agree(c, *arrays, what=what)
+            assert gs["valid"] == 1, what
 
 
 N_BULK, AT_LEAST = 300, 20

@@ -297,6 +297,15 @@ def test_workspace_reuse(ctx):
                              ("small, more keys than events use", small, 80)):
         res, *_ = _agree(ctx, ev, n_keys, what=what)
         assert (res["verdict"] == abi.LC_VALID).all()
+    # the mix of sizes flips while the total stays about the same: on a fresh
+    # context the per-event arrays shrink and the per-key arrays grow, so every
+    # array moves inside a workspace that does not grow, and back
+    one = np.array(ER.pairs_key(0, 800), dtype=np.int64).astype(np.int32)
+    many = ER.interleave([ER.pairs_key(k, 4, proc_base=k % 5) for k in range(150)], seed=11)
+    with abi.Context(device_mask=1) as c:
+        for what, ev, n_keys in (("one key", one, 1), ("many keys", many, 150), ("one key again", one, 1)):
+            res, *_ = _agree(c, ev, n_keys, what=what)
+            assert (res["verdict"] == abi.LC_VALID).all()
 
 
 def test_bad_key_in_the_middle(ctx):
