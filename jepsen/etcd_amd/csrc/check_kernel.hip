@@ -73,15 +73,6 @@ constexpr int kCpN = 30;
 __device__ unsigned long long g_cp[4096][2][kCpN];  // waves 0 and 1
 #define CP_NOW() __builtin_amdgcn_s_memtime()
 #endif
-#ifdef HBM_PROFILE
-// Dev only (tools/build_variants.sh NAME -DHBM_PROFILE): per cooperative
-// return, by log2 of its larger set: returns, device ticks (100 MHz), LDS-
-// mode returns, configurations explored; printed by the last workgroup.
-__device__ unsigned long long g_hhist[20][4];
-// per workgroup: ticks in LDS-mode returns, in HBM-mode returns (incl. failed LDS attempts), whole keys
-__device__ unsigned long long g_hwg[4096][3];
-__device__ unsigned int g_hdone;
-#endif
 
 struct Cfg {
   uint64_t mask;  // bit t: the op in window slot t is linearized
@@ -439,10 +430,7 @@ struct HbmStore {
 // role's set; the pool holds 12-byte configurations plus a 1-byte ready flag
 // (CoopTab): 1,688 in a 4-wave workgroup's 40 KB (four per CU), 3,456 in an
 // 8- or 16-wave one's 80 KB.
-#ifndef LC_LEPOCH_MASK
-#define LC_LEPOCH_MASK 0xFFu  // (8 bits: wrdy; a dev build with 0x3 wraps every 3 returns)
-#endif
-constexpr uint32_t kLepochMask = LC_LEPOCH_MASK;
+constexpr uint32_t kLepochMask = 0xFFu;  // (8 bits: wrdy)
 constexpr int kSpinMax = 1 << 22;       // queue waits (s_sleep 1 each) before giving up
 constexpr uint32_t kIdxBusy = 0xFFFFu;  // claimed, index not yet published
 constexpr uint32_t kIdxOvf = 0xFFFEu;   // claimed past the pool (the return is redone)
@@ -509,14 +497,10 @@ struct DeferF<S, std::void_t<decltype(S::kLT)>> {
 // waves on its SIMD (model_leg 9.22 -> 8.88 ms; raising the expansion
 // waves' too, or dropping wave 0's during its share of the expansion,
 // measured slower: profiles/r06/model_prio_ab.txt)
-#ifndef LC_COOP_PRIO
-#define LC_COOP_PRIO 3
-#endif
+constexpr int kCoopPrio = 3;
 // Sleep of a wave whose work queue is empty while others expand, or whose
 // claimed entries are not yet written (s_sleep units of 64 clocks)
-#ifndef LC_COOP_SLEEP
-#define LC_COOP_SLEEP 1
-#endif
+constexpr int kCoopSleep = 1;
 // LDS-only fences: the tables are workgroup-private, so publishing an entry
 // waits for LDS (lgkmcnt) only, not for the wave's global R appends.
 __device__ __forceinline__ void lds_release() {
@@ -930,7 +914,7 @@ __device__ void coop_expand(HbmStore &st, CoopShared &C, int lane, int wave) {
 #ifdef LC_COOP_PROF
             qsp++;
 #endif
-            __builtin_amdgcn_s_sleep(LC_COOP_SLEEP);
+            __builtin_amdgcn_s_sleep(kCoopSleep);
           }
         }
         k = uni(k);
@@ -962,7 +946,7 @@ __device__ void coop_expand(HbmStore &st, CoopShared &C, int lane, int wave) {
               ovf = true;
               break;
             }
-            __builtin_amdgcn_s_sleep(LC_COOP_SLEEP);
+            __builtin_amdgcn_s_sleep(kCoopSleep);
           }
         if (__ballot(ovf)) {
           if (lane == 0) {
@@ -1118,9 +1102,6 @@ __device__ int coop_return(CoopStore<LT> &st, const Slot &sl, const Masks &mk, i
   bool lds = nF <= kPool && st.lsum <= 2 * kPool;
   const uint32_t floor = max(1024u, 256u * (uint32_t)st.nwaves);
   if (!lds) st.tmask = st.pick_tmask(nF, floor);
-#ifdef HBM_PROFILE
-  const uint64_t tr0 = wall_clock64();
-#endif
 #ifdef LC_COOP_PROF
   const uint64_t cr0 = CP_NOW();
   st.cp[23] += cr0 - ce0;
@@ -1186,19 +1167,6 @@ __device__ int coop_return(CoopStore<LT> &st, const Slot &sl, const Masks &mk, i
       st.tmask = st.grow_tmask();
     }
   }
-#ifdef HBM_PROFILE
-  if (lane == 0 && C.status == 0) {
-    const int mx = max(C.nR, C.nW);
-    const int bkt = min(19, 32 - __builtin_clz((unsigned)max(mx, 1)));
-    atomicAdd(&g_hhist[bkt][0], 1ull);
-    atomicAdd(&g_hhist[bkt][1], (unsigned long long)(wall_clock64() - tr0));
-    atomicAdd(&g_hhist[bkt][2], (unsigned long long)lds);
-    atomicAdd(&g_hhist[bkt][3], (unsigned long long)(C.explored - (unsigned long long)o.explored));
-  }
-  if (lane == 0 && blockIdx.x < 4096) {
-    g_hwg[blockIdx.x][lds ? 0 : 1] += wall_clock64() - tr0;
-  }
-#endif
 #ifdef LC_COOP_PROF
   st.cp[6] += CP_NOW() - cr0;
   st.cp[8]++;
@@ -1790,38 +1758,15 @@ __global__ __launch_bounds__(kWave *kWavesPerWG) void frontier_dump_kernel(
 // versions, a read [nil x], more than kFastMax records, malformed records) or
 // finds invalid are handed to the JIT search, which also names the canonical
 // counterexample.
-#ifndef LC_FAST_DEV
-#define LC_FAST_DEV 0  // dev timing switches (tools/build_variants.sh); 0 in the product
-#endif
-// The version-order and fused kernels: one workgroup per key (0), or
-// persistent workgroups that issue the next key's loads while deciding a key
-// from LDS (1, fast_run; more VGPRs per thread, measured slower: DESIGN.md).
-#ifndef LC_PIPE
-#define LC_PIPE 0
-#endif
-// The version-order tier's pass 1: the case analysis the fused and
-// crash-light passes run (1), or a branch-free form (0, A/B: 952 -> 723
-// instructions and 52 -> 10 branches per wave, but 61 -> 76 VGPRs in
-// fast_tier_kernel and 17 spilled in the resident grid's 80: C2's kernel
-// unchanged, the resident 1,250-key request 15.1 -> 21.3 us;
-// profiles/r06/pass_ab.txt)
-#ifndef LC_FAST_P1_BRANCHY
-#define LC_FAST_P1_BRANCHY 1
-#endif
-// The resident grid's decision: the version-order tier's two record passes
-// (1), or value claims as LDS compare-and-swaps in the one pass (0, as the
-// fused pass)
-#ifndef LC_RES_TWO_PASS
-#define LC_RES_TWO_PASS 1
-#endif
-// The other workgroups' polls of workgroup 0's copy: s_sleep between polls,
-// and one word per poll (1) or every word (0)
-#ifndef LC_RES_SLEEP
-#define LC_RES_SLEEP 4
-#endif
-#ifndef LC_RES_POLL1
-#define LC_RES_POLL1 0
-#endif
+// The version-order and fused kernels run one workgroup per key, and the
+// version-order tier's pass 1 is the case analysis the fused and crash-light
+// passes run.  (Persistent workgroups that load the next key while deciding
+// one, and a branch-free pass 1, both measured slower: DESIGN.md,
+// profiles/r06/pass_ab.txt.)
+
+// The resident grid's workgroups other than 0 poll every word of workgroup
+// 0's copy of the request, with this s_sleep between polls
+constexpr int kResSleep = 4;
 constexpr int kFastThreads = 256;
 constexpr int kFastWaves = kFastThreads / kWave;
 constexpr int kFastMax = kFastMaxRecords;
@@ -1882,7 +1827,7 @@ __device__ __forceinline__ void put_result(lc_key_result *o, const lc_key_result
 __device__ __forceinline__ void fast_tier_handoff(int64_t key, int32_t *flags, KStatus *status,
                                                   int32_t *h_handoff, bool jit_only, int *raised) {
   flags[key] = jit_only ? 2 : 1;
-  // once per workgroup (the persistent kernels decide many keys each): the
+  // once per workgroup (the resident grid's decide many keys each): the
   // device-side word is read with every load in flight drained first
   if (*raised) return;
   *raised = 1;
@@ -1946,9 +1891,9 @@ struct FastRecs {
 
 // Issue every load of this thread's records without waiting: up to 4 x 48 B
 // per thread, 48 KB per workgroup in flight.  Vector loads only: a scalar
-// load in flight holds up every LDS wait (lgkmcnt) of the key the persistent
-// kernels decide meanwhile, so the order check takes lane 0's predecessor
-// from LDS (FastLds::last_call) and the key's first call arrives the same way.
+// load in flight holds up every LDS wait (lgkmcnt) behind it, so the order
+// check takes lane 0's predecessor from LDS (FastLds::last_call) and the
+// key's first call arrives the same way.
 __device__ __forceinline__ void fast_issue(const lc_op *__restrict__ kops, int n, int tid,
                                            FastRecs &b) {
 #pragma unroll
@@ -1960,7 +1905,7 @@ __device__ __forceinline__ void fast_issue(const lc_op *__restrict__ kops, int n
       b.w[u].b = q[1];
       b.w[u].c = q[2];
     } else {
-      // (defined either way: the persistent kernels' registers then carry no
+      // (defined either way: the resident grid's registers then carry no
       // value of the key before across the loads)
       b.w[u].a = b.w[u].b = b.w[u].c = make_longlong2(0, 0);
     }
@@ -2078,14 +2023,8 @@ __device__ __forceinline__ bool timing_fails(const FastLds &s, int M, int tid) {
 // positions); anything else — invalid (the gap tier bisects for the fail
 // op), more than kFgMaxGaps gaps or kFgMaxOps optional ops, a crashed op
 // that carries a version, the branch budget — is handed over as before.
-#ifndef LC_FG_MAXGAPS
-#define LC_FG_MAXGAPS 48
-#endif
-#ifndef LC_FG_MAXOPS
-#define LC_FG_MAXOPS 96
-#endif
-constexpr int kFgMaxGaps = LC_FG_MAXGAPS;
-constexpr int kFgMaxOps = LC_FG_MAXOPS;
+constexpr int kFgMaxGaps = 48;
+constexpr int kFgMaxOps = 96;
 // dynamic LDS: the matching region at its largest (gapmatch.h layout without
 // the class table: 16 B + 5 ints per gap, 16 B + 7 ints per op), then the
 // optional ops' record indices and the branch stack (gap, value)
@@ -2127,8 +2066,7 @@ __device__ __forceinline__ int fg_prefix_wave(int v, FastLds &s, int tid) {
 // Returns true when the key was decided valid here; false: hand it over.
 // Works from LDS alone: pass 1 (fast_key) already claimed the values, took
 // the extents and stashed the optional ops (kFgStash per wave, in record
-// order), so the records' registers are free for the next key's loads
-// (the persistent version-order / fused kernels) while this runs.
+// order), so the records' registers are dead while this runs.
 // NM: mutations placed by pass 1 over the workgroup.
 __device__ __forceinline__ bool fast_gap(int64_t key, int n, int NM, const KParams &p, FastLds &s,
                          lc_key_result *__restrict__ out, int32_t *__restrict__ wit,
@@ -2257,10 +2195,6 @@ __device__ __forceinline__ bool fast_gap(int64_t key, int n, int NM, const KPara
     if (tb.x | tb.y | tb.z | tb.w) return false;
   }
   if (G > n_opt) return false;  // invalid: the gap tier names the fail op
-#ifdef LC_FG_NOMATCH  // dev timing only: everything but the matching
-  if (tid == 0) out[key] = lc_key_result{LC_VALID, LC_REASON_NONE, -1, -1, 0, G};
-  return true;
-#endif
   int res = GD_VALID;
   int64_t nodes = 0;
   if (G > 0 && w == 0) {
@@ -2540,12 +2474,18 @@ __device__ __forceinline__ void fast_pass_on(int64_t key, const FastSinks &o, in
 
 // Decide one key (records in b when 0 < n64 <= kFastMax) or hand it over.
 // Three barriers: after the LDS init, after pass 1, before thread 0 reads
-// the per-wave verdicts.  Pass 1 is the only pass over the records (value
-// claims are LDS compare-and-swaps, FastLds), so once it is done the
-// records' registers are free: `next()` — called once by every thread, there
-// or at once for a key with nothing to decide — lets the persistent kernels
-// issue the next key's loads into them while this key is decided from LDS.
-// The crash-light pass (kModeLight) keeps the records for first_failure.
+// the per-wave verdicts.  In the fused and crash-light modes pass 1 is the
+// only pass over the records (value claims are LDS compare-and-swaps,
+// FastLds); the version-order mode (kModeFast) checks the claims in a second
+// pass over the registers.  The crash-light pass (kModeLight) keeps the
+// records for first_failure.
+// `next()` is called once by every thread, where the fused pass is done with
+// the records or at once for a key with nothing to decide.  Every caller
+// passes a no-op: the persistent kernels that loaded the next key there are
+// gone.  The parameter outlived them because dropping it changes the code
+// the compiler emits for the five kernels built on fast_one / fast_one32
+// (their record loads' PHI nodes come out in another order, so registers and
+// a few waits and branches differ): remove it together with a measurement.
 // RES: the resident grid (below) — the key's first call comes through LDS
 // (thread 0 holds record 0) instead of a load that may be served from a
 // cache filled in an earlier request, and results are written through.
@@ -2554,11 +2494,11 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
                                          int64_t kbase, const Recs &b, const KParams &p, FastLds &s,
                                          lc_key_result *__restrict__ out, const FastSinks &o,
                                          int32_t *__restrict__ wit, Next &&next) {
-  // the thread index, opaque to the compiler: in the persistent kernels'
-  // loop everything derived from it (LDS addresses, lane masks) would
-  // otherwise be hoisted out and held in VGPRs across every key
+  // the thread index, opaque to the compiler: in the resident grid's loop
+  // everything derived from it (LDS addresses, lane masks) would otherwise
+  // be hoisted out and held in VGPRs across every key
   int tid = threadIdx.x;
-  if constexpr (LC_PIPE || RES) asm volatile("" : "+v"(tid));
+  if constexpr (RES) asm volatile("" : "+v"(tid));
   const int lane = tid & (kWave - 1), w = __builtin_amdgcn_readfirstlane(tid / kWave);
   if (n64 <= 0 || n64 > kFastMax) {
     next();
@@ -2573,18 +2513,6 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
   const int n = (int)n64;
   FGP_T(0);
   FP_T(0);
-#if LC_FAST_DEV == 2  // dev timing only: loads, no decision
-  {
-    int64_t x = 0;
-#pragma unroll
-    for (int u = 0; u < kPer; u++)
-      x ^= b.w[u].a.x ^ b.w[u].a.y ^ b.w[u].b.x ^ b.w[u].b.y ^ b.w[u].c.x ^ b.w[u].c.y;
-    next();
-    if (x == 0x123456789) out[key].configs_explored = x;
-    if (tid == 0) out[key] = lc_key_result{LC_VALID, LC_REASON_NONE, -1, -1, 0, 1};
-    return;
-  }
-#endif
   // thread t clears positions 4t..4t+3 of A, B, Own and Val (one 16-byte
   // store each, 8 for Own); A[kFastMax] (reads of the version after the last
   // possible mutation) by thread 0, which also publishes the key's first call
@@ -2592,11 +2520,11 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
     reinterpret_cast<uint4 *>(s.A)[tid] = make_uint4(0, 0, 0, 0);  // nothing constrains t_k from below
     reinterpret_cast<uint4 *>(s.B)[tid] = make_uint4(kNever, kNever, kNever, kNever);
     reinterpret_cast<uint2 *>(s.Own)[tid] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-    if (MODE != kModeFast || LC_PIPE || (RES && !LC_RES_TWO_PASS))  // (claimed values start unclaimed)
+    if (MODE != kModeFast)  // (claimed values start unclaimed)
       reinterpret_cast<int4 *>(s.Val)[tid] = make_int4(kAny, kAny, kAny, kAny);
   }
   int64_t base_idx;
-  if constexpr (LC_PIPE || RES) {
+  if constexpr (RES) {
     if (tid == 0) {
       s.A[kFastMax] = 0;
       s.base = rec_raw(b, 0, kbase).c.x;
@@ -2617,12 +2545,12 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
   uint32_t optc = 0;   // per chunk, one byte each
   int4 *stash = reinterpret_cast<int4 *>(reinterpret_cast<char *>(lds_dyn) + kFgStashOff) +
                 w * kFgStash;
-  // The version-order tier (one workgroup per key) keeps its records in
+  // The version-order tier (the resident grid included) keeps its records in
   // registers through the decision: it stores each placed mutation's value
   // and checks the claims in a second pass over the registers (measured ~2 %
   // faster on C2 than the compare-and-swaps); the fused and light passes
   // claim in pass 1 and free the records.
-  constexpr bool kTwoPass = MODE == kModeFast && !LC_PIPE && !(RES && !LC_RES_TWO_PASS);
+  constexpr bool kTwoPass = MODE == kModeFast;
   auto claim = [&](int k, int v) {  // value v required at version V0+k+1 (k >= 0)
     if constexpr (!kTwoPass) {
       const int old = atomicCAS(&s.Val[k], kAny, v);
@@ -2631,60 +2559,6 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
   };
   // pass 1: place mutations, fold read intervals into A / B, claim values,
   // stash crashed writes/CAS
-  if constexpr (MODE == kModeFast && kTwoPass && !LC_FAST_P1_BRANCHY) {
-    // The version-order tier's pass 1, branch-free (the same placements,
-    // bounds and flags as the case analysis below, which the fused and
-    // crash-light passes keep): every record issues its two LDS atomics and
-    // two stores, a record that places nothing aimed at a no-op — max with
-    // 0, min with kNever, stores into the arrays' spare slot kFastMax + 1 —
-    // so the wave runs one straight line per record instead of ~13 masked
-    // branches
-    constexpr int kSpare = kFastMax + 1;
-#pragma unroll
-    for (int u = 0; u < kPer; u++) {
-      const int r = tid + u * kFastThreads;
-      auto &&bw = rec_raw(b, u, kbase);
-      const Rec d = decode(bw, base_idx);
-      const uint32_t prev = (uint32_t)wave_shr1((int)d.call, 0);
-      // (a chunk's first call is read only when its first record is live,
-      // its last call only when the next chunk's first is)
-      if (lane == 0) s.first_call[u][w] = d.call;
-      if (lane == kWave - 1) s.last_call[u][w] = d.call;
-      const bool live = r < n;
-      const bool brec = live & (d.bad | (d.f > LC_F_CAS) | ((lane > 0) & (prev >= d.call)));
-      const bool ok = live & !brec;
-      const bool is_read = d.f == LC_F_READ;
-      // reads: a returned read other than [nil nil] constrains; [nil x] is
-      // the JIT tier's; a version index outside [0, n] no state reaches
-      const bool rd = ok & is_read & (d.ret != kNever) & !((d.ver == -1) & (d.val == -1));
-      const bool rd_nil = rd & (d.ver == -1);
-      const int k = d.ver - V0;
-      const bool rd_v = rd & (d.ver != -1);
-      const bool rd_bad = rd_v & ((k < 0) | (k > n));
-      const bool rd_ok = rd_v & !rd_bad;
-      // mutations: crashed or version-less ones are not pinned
-      const bool mu = ok & !is_read;
-      const bool mu_crash = mu & (d.ret == kNever), mu_nover = mu & (d.ver == -1);
-      const int pos = d.ver - V0 - 1;
-      const bool mu_v = mu & !mu_crash & !mu_nover;
-      const bool mu_bad = mu_v & ((pos < 0) | (pos >= n));
-      const bool mu_ok = mu_v & !mu_bad;
-      atomicMax(&s.A[rd_ok ? k : mu_ok ? pos : kSpare], (rd_ok | mu_ok) ? d.call + 1 : 0u);
-      atomicMin(&s.B[rd_ok && k > 0 ? k - 1 : mu_ok ? pos : 0],
-                ((rd_ok & (k > 0)) | mu_ok) ? d.ret : kNever);
-      const int ps = mu_ok ? pos : kSpare;
-      s.Own[ps] = (uint16_t)r;
-      s.Val[ps] = d.val;
-      // the claims on the initial value (the others: pass 2)
-      vbad |= (int)((mu_ok & (d.f == LC_F_CAS) & (pos == 0) & (d.exp != init)) |
-                    (rd_ok & (k == 0) & (d.val != -1) & (d.val != init)));
-      inel |= (int)(brec | rd_nil | mu_crash | mu_nover);
-      jit_only |= (int)(brec | rd_nil | (mu_nover & !mu_crash));
-      giveup |= (int)(mu_crash & (d.ver != -1));
-      bad |= (int)(rd_bad | mu_bad);
-      nmut += __popcll(__ballot(mu_ok));
-    }
-  } else
 #pragma unroll
   for (int u = 0; u < kPer; u++) {
     const int r = tid + u * kFastThreads;
@@ -2761,7 +2635,7 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
       optc |= (uint32_t)c << (8 * u);
     }
   }
-  // the records are consumed: their registers take the next key's loads
+  // the records are consumed
   if constexpr (MODE != kModeLight) next();
   // (ballots outside the lane-0 branch: they must see every lane)
   uint32_t fl = 0;
@@ -2805,12 +2679,6 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
     if (__ballot(ob)) wor |= kSumInel | kSumJit;
   }
   FGP_T(4);
-#ifdef LC_FG_STOP1  // dev timing only: the fused pass stops after pass 1
-  if (MODE == kModeFused) {
-    if (tid == 0) out[key] = lc_key_result{LC_VALID, LC_REASON_NONE, -1, -1, 0, 1};
-    return;
-  }
-#endif
   if (wor & kSumElig) {  // ineligible or a version out of range: hand over
     // crash-light pass: crashed writes/CAS are the only obstacle
     if constexpr (MODE != kModeFast)
@@ -2920,50 +2788,6 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
   }
 }
 
-// The version-order and fused kernels: persistent workgroups (as many as
-// are resident, lincheck.cpp sizes the grid), each deciding keys blockIdx.x,
-// + gridDim.x, ... .  A key's loads are issued while the key before it is
-// decided from LDS (fast_key's next()): one register set, the records in
-// flight during the decision instead of the decision and the loads taking
-// turns.  The next key's offsets come one key ahead, by vector loads (two
-// lanes) for the same reason as fast_issue's.
-template <int MODE>
-__device__ __forceinline__ void fast_run(const lc_op *__restrict__ ops,
-                                         const int64_t *__restrict__ key_off, int64_t n_keys,
-                                         const KParams &p, FastLds &s,
-                                         lc_key_result *__restrict__ out, const FastSinks &o) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int64_t off0 = key_off[0];
-  int64_t key = blockIdx.x;
-  if (key >= n_keys) return;
-  if (tid == 0) s.raised = 0;
-  int64_t beg = key_off[key], end = key_off[key + 1];
-  FastRecs r;
-  if (end - beg > 0 && end - beg <= kFastMax) fast_issue(ops + (beg - off0), (int)(end - beg), tid, r);
-  // the next key's offsets (lanes 0 and 1)
-  int64_t nx = key + gridDim.x;
-  int64_t offv = 0;
-  if (nx < n_keys && lane < 2) offv = key_off[nx + lane];
-  for (;;) {
-    int64_t nbeg = 0, nend = 0;
-    const int64_t nx2 = nx + gridDim.x;
-    auto next = [&]() {
-      nbeg = __shfl(offv, 0);
-      nend = __shfl(offv, 1);
-      const int64_t nn = nx < n_keys ? nend - nbeg : 0;
-      fast_issue(ops + (nbeg - off0), nn > 0 && nn <= kFastMax ? (int)nn : 0, tid, r);
-      if (nx2 < n_keys && lane < 2) offv = key_off[nx2 + lane];
-    };
-    fast_key<MODE>(key, end - beg, ops + (beg - off0), 0, r, p, s, out, o,
-                   o.wit ? o.wit + (beg - off0) : nullptr, next);
-    if (nx >= n_keys) break;
-    key = nx;
-    beg = nbeg;
-    end = nend;
-    nx = nx2;
-  }
-}
-
 template <int MODE>
 __device__ __forceinline__ void fast_one(const lc_op *__restrict__ ops,
                                          const int64_t *__restrict__ key_off, int64_t key,
@@ -2993,7 +2817,6 @@ __device__ __forceinline__ void fast_one32(const lc_op32 *__restrict__ ops,
                                            const int64_t *__restrict__ key_base, int64_t key,
                                            const KParams &p, FastLds &s,
                                            lc_key_result *__restrict__ out, const FastSinks &o) {
-  static_assert(!LC_PIPE, "the 24-byte pass reads its base per key, not from LDS (LC_PIPE)");
   const int64_t beg = key_off[key], end = key_off[key + 1];
   const lc_op32 *kops = ops + (beg - key_off[0]);
   const int64_t kbase = key_base ? key_base[key] : 0;
@@ -3016,11 +2839,7 @@ __global__ __launch_bounds__(kFastThreads) void fast_tier_kernel(
     int32_t *__restrict__ h_handoff) {
   __shared__ FastLds s;
   const FastSinks o{flags, status, h_handoff, nullptr, nullptr, nullptr};
-#if LC_PIPE
-  fast_run<kModeFast>(ops, key_off, n_keys, p, s, out, o);
-#else
   fast_one<kModeFast>(ops, key_off, blockIdx.x, p, s, out, o);
-#endif
 #ifdef LC_FAST_PROF
   if (threadIdx.x == 0 && atomicAdd(&g_fpdone, 1u) == gridDim.x - 1) {
     printf("fastprof keys %u offsets %llu land+init %llu pass1 %llu order+pass2 %llu timing %llu result %llu\n",
@@ -3146,20 +2965,6 @@ __global__ __launch_bounds__(kFastThreads, 6) void fast_resident_kernel(ResHost 
       uint64_t w = 0;
       bool leave = false;
       for (uint32_t polls = 0;; polls++) {
-        if (!first && LC_RES_POLL1) {
-          // one word per poll (the others only once it carries the number):
-          // 1,249 pollers beside the record stream
-          const uint64_t w0 = __hip_atomic_load(src + kResWords - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((uint32_t)(__builtin_amdgcn_readfirstlane((int)(uint32_t)(w0 >> 32)) >> 16) != want) {
-            const uint64_t now = wall_clock64();
-            if (now - t0 > kResStrayTicks || polls >= kResPollCap) {
-              leave = true;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(LC_RES_SLEEP);
-            continue;
-          }
-        }
         if (tid < kResWords)
           w = first ? __hip_atomic_load(src + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
                     : __hip_atomic_load(src + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3171,7 +2976,7 @@ __global__ __launch_bounds__(kFastThreads, 6) void fast_resident_kernel(ResHost 
           break;
         }
         if (first) __builtin_amdgcn_s_sleep(1);
-        else __builtin_amdgcn_s_sleep(LC_RES_SLEEP);
+        else __builtin_amdgcn_s_sleep(kResSleep);
       }
       if (leave) {
         // workgroup 0 on its idle bound: says so, and hands the others an
@@ -3227,11 +3032,8 @@ __global__ __launch_bounds__(kFastThreads, 6) void fast_resident_kernel(ResHost 
 // 4 waves per SIMD (at most 128 VGPRs): left alone the compiler takes 138
 // (3 waves); 4 has no VGPR spills and decides bench.py's crash_leg in
 // 0.24 ms against 0.29 ms (5 and 6 waves spill: 0.33 / 0.36 ms).
-#ifndef LC_LIGHT_WPE
-#define LC_LIGHT_WPE 4
-#endif
-#define LC_LIGHT_ATTR __attribute__((amdgpu_waves_per_eu(LC_LIGHT_WPE, 8)))
-__global__ __launch_bounds__(kFastThreads) LC_LIGHT_ATTR void gap_light_kernel(
+constexpr int kLightWpe = 4;  // (the fused kernels' too)
+__global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(kLightWpe, 8))) void gap_light_kernel(
     const lc_op *__restrict__ ops, const int64_t *__restrict__ key_off,
     const int32_t *__restrict__ keys, const KParams p, lc_key_result *__restrict__ out,
     const FastSinks o) {
@@ -3248,22 +3050,15 @@ __global__ __launch_bounds__(kFastThreads) LC_LIGHT_ATTR void gap_light_kernel(
 }
 
 // The version-order tier and the crash-light decision in one pass over every
-// key (kModeFused), persistent as the version-order tier; keys it does not
-// decide are flagged for the same handoff compaction.  The crash-light
+// key (kModeFused), one workgroup per key as the version-order tier; keys it
+// does not decide are flagged for the same handoff compaction.  The crash-light
 // register budget — the host picks this kernel only for batches where most
 // keys carry crashed ops (lincheck.cpp).
-#ifndef LC_FUSED_WPE
-#define LC_FUSED_WPE LC_LIGHT_WPE
-#endif
-__global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(LC_FUSED_WPE, 8))) void fused_tier_kernel(
+__global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(kLightWpe, 8))) void fused_tier_kernel(
     const lc_op *__restrict__ ops, const int64_t *__restrict__ key_off, int64_t n_keys,
     const KParams p, lc_key_result *__restrict__ out, const FastSinks o) {
   __shared__ FastLds s;
-#if LC_PIPE
-  fast_run<kModeFused>(ops, key_off, n_keys, p, s, out, o);
-#else
   fast_one<kModeFused>(ops, key_off, blockIdx.x, p, s, out, o);
-#endif
 #ifdef LC_FG_PROF
   if (threadIdx.x == 0 && atomicAdd(&g_fgdone, 1u) == gridDim.x - 1) {
     printf("fgprof keys-wg %u entry->init %llu init->pass1 %llu pass1->light %llu scans %llu match %llu "
@@ -3276,7 +3071,7 @@ __global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(LC
 }
 
 // The fused pass over lc_op32 records (as fast_tier32_kernel)
-__global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(LC_FUSED_WPE, 8))) void fused_tier32_kernel(
+__global__ __launch_bounds__(kFastThreads) __attribute__((amdgpu_waves_per_eu(kLightWpe, 8))) void fused_tier32_kernel(
     const lc_op32 *__restrict__ ops, const int64_t *__restrict__ key_off,
     const int64_t *__restrict__ key_base, int64_t n_keys, const KParams p,
     lc_key_result *__restrict__ out, const FastSinks o) {
@@ -4100,7 +3895,7 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4)))
   hbm_zero_tags(st.tags, cap);
   st.epoch = 0;  // epochs start at 1
   if (wave == 0) {
-    if (LC_COOP_PRIO) __builtin_amdgcn_s_setprio(LC_COOP_PRIO);  // (LC_COOP_PRIO above)
+    __builtin_amdgcn_s_setprio(kCoopPrio);  // (kCoopPrio above)
     const int64_t key_base = key_off[0];
     for (;;) {  // list entries claimed one at a time (next: zero at launch)
       int li = 0;
@@ -4114,9 +3909,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4)))
       st.last = st.lsum = 0;
       st.vleg = 0;
       st.fclear = st.fclose = 0;
-#ifdef HBM_PROFILE
-      const uint64_t tk0 = wall_clock64();
-#endif
 #ifdef LC_COOP_PROF
       const uint64_t ck0 = CP_NOW();
 #endif
@@ -4124,9 +3916,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4)))
 #ifdef LC_COOP_PROF
       st.cp[7] += CP_NOW() - ck0;
       st.cp[10]++;
-#endif
-#ifdef HBM_PROFILE
-      if (lane == 0 && blockIdx.x < 4096) g_hwg[blockIdx.x][2] += wall_clock64() - tk0;
 #endif
       if (o.reason == LC_REASON_FRONTIER_LDS) {
         if (last_tier)
@@ -4143,27 +3932,6 @@ __global__ __launch_bounds__(NW * kWave) __attribute__((amdgpu_waves_per_eu(4)))
 #ifdef LC_COOP_PROF
     if (lane == 0 && blockIdx.x < 4096)
       for (int q = 0; q < kCpN; q++) g_cp[blockIdx.x][0][q] = st.cp[q];
-#endif
-#ifdef HBM_PROFILE
-    __threadfence();
-    if (lane == 0 && atomicAdd(&g_hdone, 1u) == gridDim.x - 1)
-      for (int b = 0; b < 20; b++)
-        if (g_hhist[b][0])
-          printf("set<2^%d: returns %llu ticks %llu lds %llu configs %llu\n", b, g_hhist[b][0],
-                 g_hhist[b][1], g_hhist[b][2], g_hhist[b][3]);
-    if (lane == 0 && g_hdone == gridDim.x) {
-      unsigned long long sum = 0;
-      for (unsigned i = 0; i < gridDim.x && i < 4096; i++) sum += g_hwg[i][2];
-      printf("workgroups %u mean key ticks %llu\n", gridDim.x, sum / gridDim.x);
-      for (int t = 0; t < 6; t++) {
-        unsigned best = 0;
-        for (unsigned i = 0; i < gridDim.x && i < 4096; i++)
-          if (g_hwg[i][2] > g_hwg[best][2]) best = i;
-        printf("  slow wg %u: key %llu lds-returns %llu hbm-returns %llu\n", best, g_hwg[best][2],
-               g_hwg[best][0], g_hwg[best][1]);
-        g_hwg[best][2] = 0;
-      }
-    }
 #endif
     coop_barrier();
   } else {
@@ -4334,7 +4102,7 @@ hipError_t launch_witness_init(const lc_op *d_ops, const int64_t *d_key_off, int
   return hipGetLastError();
 }
 
-// Resident workgroups of a persistent kernel on the current device (its
+// Resident workgroups of the resident grid's kernel on the current device (its
 // grid): occupancy per CU x CUs, cached per device and kernel.
 template <typename K>
 static int64_t resident_wgs(K kernel, int which, size_t dyn_lds) {
@@ -4371,8 +4139,7 @@ hipError_t launch_fast_tier(const lc_op *d_ops, const int64_t *d_key_off,
                             lc_key_result *d_out, int32_t *d_flags,
                             KStatus *d_status, int32_t *h_handoff, hipStream_t stream) {
   if (n_keys <= 0) return hipSuccess;
-  const int64_t wgs = LC_PIPE ? std::min(n_keys, resident_wgs(fast_tier_kernel, 0, 0)) : n_keys;
-  hipLaunchKernelGGL(fast_tier_kernel, dim3((unsigned)wgs), dim3(kFastThreads), 0,
+  hipLaunchKernelGGL(fast_tier_kernel, dim3((unsigned)n_keys), dim3(kFastThreads), 0,
                      stream, d_ops, d_key_off, n_keys, p, d_out, d_flags, d_status, h_handoff);
   return hipGetLastError();
 }
@@ -4383,9 +4150,7 @@ hipError_t launch_fused_tier(const lc_op *d_ops, const int64_t *d_key_off, int64
                              int32_t *d_witness_kind, hipStream_t stream) {
   if (n_keys <= 0) return hipSuccess;
   const FastSinks o{d_flags, d_status, h_handoff, nullptr, d_witness, d_witness_kind};
-  const int64_t wgs =
-      LC_PIPE ? std::min(n_keys, resident_wgs(fused_tier_kernel, 1, kFgLdsBytes)) : n_keys;
-  hipLaunchKernelGGL(fused_tier_kernel, dim3((unsigned)wgs), dim3(kFastThreads),
+  hipLaunchKernelGGL(fused_tier_kernel, dim3((unsigned)n_keys), dim3(kFastThreads),
                      (unsigned)kFgLdsBytes, stream, d_ops, d_key_off, n_keys, p, d_out, o);
   return hipGetLastError();
 }

@@ -333,10 +333,6 @@ __device__ int gap_setup(const GapKey &g, const GapWs<SL> &w, uint32_t cut) {
     w.B[k] = kNever;
     w.Pin[k] = -1;
     w.Claim[k] = kAny;
-#ifdef GAP_SETUP_TOUCH  // A/B: also touch the arrays pass 1 writes first
-    w.Val[k] = 0;
-    w.PinExp[k] = kAny;
-#endif
   }
   if (tid == 0) {
     sh.flag = 0;
@@ -347,9 +343,6 @@ __device__ int gap_setup(const GapKey &g, const GapWs<SL> &w, uint32_t cut) {
     sh.n_gap = 0;
   }
   __syncthreads();
-#if GAP_STOP_AT == 1  // dev timing builds (with GAP_STOP_SETUP): end the setup early
-  return GD_VALID;
-#endif
 #ifdef GAP_PROFILE
   if (tid == 0) sh.prof[0] = wall_clock64();
 #endif
@@ -420,9 +413,6 @@ __device__ int gap_setup(const GapKey &g, const GapWs<SL> &w, uint32_t cut) {
       if (maxread >= 0) atomicMax(&sh.maxread, maxread);
       if (maxret) atomicMax(&sh.maxret, maxret);
       __syncthreads();
-#if GAP_STOP_AT == 2
-      return GD_VALID;
-#endif
 #ifdef GAP_PROFILE
     if (tid == 0) sh.prof[1] = wall_clock64();
 #endif
@@ -436,9 +426,6 @@ __device__ int gap_setup(const GapKey &g, const GapWs<SL> &w, uint32_t cut) {
   }
   if (flag) atomicOr(&sh.flag, flag);
   __syncthreads();
-#if GAP_STOP_AT == 3
-  return GD_VALID;
-#endif
 #ifdef GAP_PROFILE
     if (tid == 0) sh.prof[3] = wall_clock64();
 #endif
@@ -546,20 +533,11 @@ __device__ int gap_decide(const GapKey &g_arg, const GapWs<SL> &w_arg, uint32_t 
   const GapKey g = g_arg;
   const GapWs<SL> w = w_arg;
 #ifdef GAP_PROFILE
-#ifdef GAP_WARM  // dev: a first setup pass whose result is dropped (cold-code cost)
-  const uint64_t tw = wall_clock64();
-  (void)gap_setup<T, SL>(g, w, cut);
-  __syncthreads();
-  if (tid == 0 && blockIdx.x < 2) printf("warm setup %lu (x10ns)\n", (unsigned long)(wall_clock64() - tw));
-#endif
   const uint64_t t0 = wall_clock64();
   if (tid < 12) s_mprof[tid] = 0;
 #endif
   const int st = gap_setup<T, SL>(g, w, cut);
   if (st != GD_VALID) return st;
-#ifdef GAP_STOP_SETUP  // dev timing build: every decision ends after its setup (verdicts meaningless)
-  return GD_VALID;
-#endif
 #ifdef GAP_PROFILE
   const uint64_t t1 = wall_clock64();
 #endif

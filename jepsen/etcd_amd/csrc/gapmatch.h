@@ -450,114 +450,11 @@ __device__ int first_fit_cls(const Cmp<L> &c, int gi, const int4 gp, ClsSt &st) 
   return found;
 }
 
-// Match gap SG[d] to op SO[d] for d = 0..depth (an augmenting path found).
-template <bool L>
-__device__ __forceinline__ void flip_path(const Cmp<L> &c, int depth, int last, ClsSt &st) {
-  const int lane = threadIdx.x & (kWave - 1);
-  // the path's last op was free (so at or past its class's free cursor) and
-  // is matched now; every other op on it stays matched
-  if (lane == uni(c.at(aCls, last))) st.ma++;
-  match_fence<L>();
-  for (int d0 = 0; d0 <= depth; d0 += kWave) {
-    const int d = d0 + lane;
-    if (d <= depth) {
-      const int gg = c.at(aSG, d), oo = c.at(aSO, d);
-      c.at(aMG, gg) = oo;
-      c.at(aMO, oo) = gg;
-      if constexpr (L)
-        if (st.mgr) c.mgr()[oo] = c.gaps()[gg];
-    }
-  }
-  match_fence<L>();
-}
-
-// Augmenting path from the unmatched gap g0 (record gp0) over the class
-// cursors.  Called right after first_fit_cls failed on g0, so every free
-// cursor's head is free.  With st.mgr the op a step reaches
-// brings the record of its gap along (one LDS round trip per step).
-template <bool L>
-__device__ bool augment_cls(const Cmp<L> &c, int g0, const int4 gp0, int stamp, ClsSt &st) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const auto ops = c.ops();
-  st.p = 0;
-  cls_head(c, st, 0, &st.po, &st.pc);
-  int depth = 0, g = uni(g0);
-  int4 gp = gp0;
-  for (;;) {
-    MPROF(2, 1);
-    const bool compat = cls_compat(st, gp);
-    // lookahead: a free eligible op ends the path here (Kuhn's search would
-    // reach it only after exhausting the matched ops called before it)
-    uint32_t fcall = cls_key(st, gp, st.fc);
-    int fop = st.fo;
-    // else the first unvisited eligible op in call order
-    uint32_t call = (compat & (st.pc < (uint32_t)gp.x)) ? st.pc : kNever;
-    int o = st.po;
-    if (st.any_pin) {
-      for (int q = uni(c.at(aPH, g)); q >= 0; q = uni(c.at(aPN, q))) {
-        const int4 op = uni4(ops[q]);
-        const bool e = elig(gp, op);
-        if (uni(c.at(aMO, q)) == -1 && e && (uint32_t)op.x < fcall) {
-          fcall = (uint32_t)op.x;
-          fop = q;
-        }
-        if (uni(c.at(aVis, q)) != stamp && e && (uint32_t)op.x < call) {
-          call = (uint32_t)op.x;
-          o = q;
-        }
-      }
-    }
-    const uint32_t fbest = wave_min_u32(fcall);
-    const uint32_t best = wave_min_u32(call);
-    if (fbest != kNever) {
-      const int free_op = uni(__builtin_amdgcn_readlane(fop, first_lane(__ballot(fcall == fbest))));
-      c.at(aSG, depth) = g;
-      c.at(aSO, depth) = free_op;
-      flip_path(c, depth, free_op, st);
-      return true;
-    }
-    if (best == kNever) {  // dead end: back to the previous gap
-      if (depth == 0) return false;
-      depth--;
-      g = uni(c.at(aSG, depth));
-      gp = uni4(c.gaps()[g]);
-      continue;
-    }
-    const int wl = first_lane(__ballot(call == best));
-    const int found = uni(__builtin_amdgcn_readlane(o, wl));
-    const int head = uni(__builtin_amdgcn_readlane(st.po, wl));
-    // the op's match (and, with mgr, its gap's record) in flight together
-    const int mo = c.at(aMO, found);
-    int4 gpn = make_int4(0, 0, 0, 0);
-    if constexpr (L)
-      if (st.mgr) gpn = c.mgr()[found];
-    if (found != head) {
-      c.at(aVis, found) = stamp;  // a pinned op
-    } else if (lane == wl) {      // visited: the class's visit cursor moves past it
-      st.p++;
-      cls_head(c, st, st.p, &st.po, &st.pc);
-    }
-    c.at(aSG, depth) = g;
-    c.at(aSO, depth) = found;
-    const int m = uni(mo);
-    if (m == -1) {  // flip the path
-      flip_path(c, depth, found, st);
-      return true;
-    }
-    depth++;
-    g = m;
-    if (L && st.mgr)
-      gp = uni4(gpn);
-    else
-      gp = uni4(c.gaps()[g]);
-  }
-}
-
 // Augmenting path from the unmatched gap g0 by breadth-first search over the
-// class cursors (the default; GAP_DFS_AUG selects augment_cls).  The depth-
-// first search above visits one op per step, and each step is a chain of
-// wave reductions and LDS round trips (≈1,000 cycles on C4); here a dequeued
-// gap visits, in one lane-parallel loop, EVERY unvisited op it can reach —
+// class cursors.  The depth-first search this replaced (round 4) visited one
+// op per step, each step a chain of wave reductions and LDS round trips
+// (≈1,000 cycles on C4); here a dequeued gap visits, in one lane-parallel
+// loop, EVERY unvisited op it can reach —
 // the prefix of each compatible class up to its deadline, all matched (a free
 // one would have ended the search) — and queues their gaps.  Visits stay
 // prefixes of each class list, so every op is visited at most once and every
@@ -701,11 +598,7 @@ __device__ bool fill(const Cmp<L> &c, int G, int n_opt, int *ff, int *stamp, Cls
       bool ok;
       MCLK0(ta);
       if constexpr (CM) {
-#ifdef GAP_DFS_AUG
-        ok = augment_cls(c, gi, gp, *stamp, st);
-#else
         ok = augment_bfs_cls(c, gi, gp, *stamp, st);
-#endif
       } else {
         ok = augment(c, gi, n_opt, *stamp);
       }
@@ -823,9 +716,6 @@ __device__ int match_branch_m(const Cmp<L> &c, int G, int n_opt, P brPos, P brVa
     MCLK0(tn);
     const bool filled = fill<L, CM>(c, G, n_opt, &ff, &stamp, st);
     MCLK1(tn, 7);
-#ifdef GAP_ONE_FILL  // dev timing build: every decision ends after its first fill (verdicts meaningless)
-    return filled ? GD_VALID : GD_INVALID;
-#endif
     if (filled) {
       // the matching ignored CAS expectations after free gaps: check them.
       // PREF: every violation whose expected value some eligible op writes

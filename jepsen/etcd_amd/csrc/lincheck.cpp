@@ -52,16 +52,13 @@ constexpr int64_t kDefaultBudget = 1 << 24;   // configurations per key
 // is ~128 B per configuration of capacity (3 regions + 2 hash tables).
 // Each tier's workspace is <= 4 GiB; the first has the most waves (the
 // lane-parallel expansion is latency-bound per wave).
-// Timing events.  LC_EVENT_FLAGS (dev A/B): hipEventDisableSystemFence skips
+// Timing events.  hipEventDisableSystemFence skips
 // the event's own system-scope fence (cache writeback + invalidate) when it
 // is recorded; kernel completion already releases the kernel's writes to
 // device memory, and the one host-visible word the host reads after such an
 // event (h_handoff) is made visible by its writer with a system-scope fence
 // (fast_tier_handoff, check_kernel.hip).
-#ifndef LC_EVENT_FLAGS
-#define LC_EVENT_FLAGS hipEventDisableSystemFence
-#endif
-constexpr unsigned kEventFlags = LC_EVENT_FLAGS;
+constexpr unsigned kEventFlags = hipEventDisableSystemFence;
 constexpr int kHbmTiers = 3;
 constexpr size_t kFxEngines = 4;  // LC_FLAG_WHOLE_GPU: oversized keys searched at once
 constexpr int64_t kHbmCap[kHbmTiers] = {1 << 14, 1 << 18, 1 << 21};
@@ -100,10 +97,7 @@ constexpr int64_t kGapSkelLdsMax = 78 << 10;  // two such workgroups per CU (160
 constexpr int kGapLdsProbe = 72 << 10;
 constexpr int kGapMaxRounds = 64;
 constexpr int kGapProbeMinLen = 1024;
-#ifndef LC_GAP_WAVE_MAX_LEN
-#define LC_GAP_WAVE_MAX_LEN 256
-#endif
-constexpr int kGapWaveMaxLen = LC_GAP_WAVE_MAX_LEN;  // keys up to this long: one-wave gap-tier workgroups
+constexpr int kGapWaveMaxLen = 256;  // keys up to this long: one-wave gap-tier workgroups
 constexpr int64_t kGapWaveMinKeys = 1024;             // ... when there are more of them than this
 constexpr int64_t kGapWideMaxKeys = 64;    // at most this many keys for the gap tier ...
 constexpr int kGapWideMinLen = 2048;        // ... the longest of them this long: 512-thread workgroups

@@ -1,5 +1,5 @@
 # Dev: interleaved A/B of the oversized key, 3 rounds: default vs the env
-# assignment in $1 (e.g. LC_FX_COPY_SYNC=1), 5 checks each (min reported)
+# assignment in $1 (e.g. LC_FX_TABLE_MUL=8), 5 checks each (min reported)
 mkdir -p gpurun_out/fx
 for i in 1 2 3; do
   timeout -k 10 120 python -u tools/fx_once.py --reps 5 > gpurun_out/fx/a$i.txt 2>&1 || { tail -20 gpurun_out/fx/a$i.txt; exit 1; }
