@@ -1,6 +1,6 @@
 // counted.h — the counted-class layout rule (include/lincheck.h,
 // lc_counted_plan / LC_FLAG_COUNTED_CLASSES), shared by the host planner
-// (lincheck.cpp) and the counted tier (check_kernel.hip): both must cut a
+// (plan_host.h) and the counted tier (check_kernel.hip): both must cut a
 // configuration's 64-bit mask into the same fields.
 //
 // Classes: the distinct (f, value, expected, version) among a key's crashed
@@ -13,7 +13,12 @@
 // slots for every other open op.  A key fits with at most kCountedMaxClasses
 // classes and at least one slot.
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define LCCOUNT_FN __host__ __device__ inline
+#else  // the host planner under g++ (plan_host.h): plain functions
+#define LCCOUNT_FN inline
+#endif
 #include <stdint.h>
 
 namespace lccount {
@@ -22,12 +27,12 @@ constexpr int kCountedMaxClasses = 16;
 
 // A version as the device reads it (records.h decode): one outside
 // [-1, 2^31-2] is a version no state reaches, saturated to 2^31-2.
-__host__ __device__ inline int64_t counted_version(int64_t v) {
+LCCOUNT_FN int64_t counted_version(int64_t v) {
   return (v < -1 || v > 0x7FFFFFFE) ? 0x7FFFFFFE : v;
 }
 
 // floor(log2(members)) + 1 for members >= 1.
-__host__ __device__ inline int counted_width(int64_t members) {
+LCCOUNT_FN int counted_width(int64_t members) {
   int w = 0;
   while (members > 0) {
     w++;
@@ -36,13 +41,15 @@ __host__ __device__ inline int counted_width(int64_t members) {
   return w;
 }
 
-__host__ __device__ inline int counted_slots(int field_bits, int n_classes) {
+LCCOUNT_FN int counted_slots(int field_bits, int n_classes) {
   const int a = 64 - field_bits, b = 64 - n_classes;
   return a < b ? a : b;
 }
 
-__host__ __device__ inline int counted_fits(int n_classes, int slots) {
+LCCOUNT_FN int counted_fits(int n_classes, int slots) {
   return n_classes <= kCountedMaxClasses && slots >= 1;
 }
 
 }  // namespace lccount
+
+#undef LCCOUNT_FN

@@ -13,30 +13,24 @@
 // the caller's array.  There is no CPU fallback: without a usable GPU lc_open
 // fails with -ENODEV.
 //
-// This file is the register path and the context.  The side checkers
+// This file is the context and the device side of the register path: the
+// tiers over keys whose arrays are on a device (run_device) and
+// lc_check_device.  lc_check from host memory is check_host.cpp, the
+// frontier calls frontiers_dev.cpp, LC_FLAG_WHOLE_GPU whole_gpu.cpp, the
+// planners and packers plan_host.cpp (plain C++); the side checkers
 // (lc_check_events, lc_set_full, lc_append_check) have their drivers in
-// *_dev.cpp; runtime.h is what those share with this file.
+// *_dev.cpp.  runtime.h is what all of those share with this file.
 #include <errno.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
-#include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "../../../include/lincheck.h"
-#include "../../../include/lincheck_fx.h"
-#include "kernels.h"
-#include "counted.h"
 #include "runtime.h"
 
 #ifndef LC_BUILD_ID
@@ -47,11 +41,6 @@ using namespace lcrt;
 
 namespace {
 
-constexpr int64_t kDefaultBudget = 1 << 24;   // configurations per key
-// HBM tiers: (configurations per set, concurrent keys).  Workspace per key
-// is ~128 B per configuration of capacity (3 regions + 2 hash tables).
-// Each tier's workspace is <= 4 GiB; the first has the most waves (the
-// lane-parallel expansion is latency-bound per wave).
 // Timing events.  hipEventDisableSystemFence skips
 // the event's own system-scope fence (cache writeback + invalidate) when it
 // is recorded; kernel completion already releases the kernel's writes to
@@ -59,10 +48,6 @@ constexpr int64_t kDefaultBudget = 1 << 24;   // configurations per key
 // event (h_handoff) is made visible by its writer with a system-scope fence
 // (fast_tier_handoff, check_kernel.hip).
 constexpr unsigned kEventFlags = hipEventDisableSystemFence;
-constexpr int kHbmTiers = 3;
-constexpr size_t kFxEngines = 4;  // LC_FLAG_WHOLE_GPU: oversized keys searched at once
-constexpr int64_t kHbmCap[kHbmTiers] = {1 << 14, 1 << 18, 1 << 21};
-constexpr int kHbmWaves[kHbmTiers] = {2048, 128, 16};
 // LC_FLAG_SEARCH_WITNESS: the witness search's workspace at most (512 KB of
 // cache per wave, 49 B per record of the longest listed key)
 constexpr size_t kWitnessWsBytes = size_t(2) << 30;
@@ -109,15 +94,26 @@ void lcrt::set_err(lc_ctx *c, const std::string &s) {
   c->err = s;
 }
 
-namespace {
+int lcrt::check_offsets(lc_ctx *c, const char *who, const int64_t *key_off, int64_t n_keys) {
+  if (key_off[0] < 0) {
+    set_err(c, std::string(who) + ": key_off[0] < 0");
+    return -EINVAL;
+  }
+  for (int64_t k = 0; k < n_keys; k++)
+    if (key_off[k + 1] < key_off[k]) {
+      set_err(c, std::string(who) + ": key_off not monotone at key " + std::to_string(k));
+      return -EINVAL;
+    }
+  return 0;
+}
 
 // NAME=0 in the environment: a path's switch, read where the path is chosen
-bool env_is_off(const char *name) {
+bool lcrt::env_is_off(const char *name) {
   const char *e = getenv(name);
   return e && e[0] == '0';
 }
 
-int opts_to_params(lc_ctx *c, const lc_opts *o, lcdev::KParams *p) {
+int lcrt::opts_to_params(lc_ctx *c, const lc_opts *o, lcdev::KParams *p) {
   lc_opts d;
   lc_default_opts(&d);
   if (!o) o = &d;
@@ -142,7 +138,7 @@ int opts_to_params(lc_ctx *c, const lc_opts *o, lcdev::KParams *p) {
 }
 
 // Is [p, p + n) inside a buffer registered with lc_host_register?
-bool is_pinned(lc_ctx *c, const void *p, size_t n) {
+bool lcrt::is_pinned(lc_ctx *c, const void *p, size_t n) {
   std::lock_guard<std::mutex> g(c->pin_mu);
   const char *q = static_cast<const char *>(p);
   for (const auto &pr : c->pinned)
@@ -150,43 +146,9 @@ bool is_pinned(lc_ctx *c, const void *p, size_t n) {
   return false;
 }
 
-// lc_check's host-to-device pipeline on one device: the device's key range
-// cut into chunks of about kChunkBytes of records.  run_device calls
-// issue(i), which enqueues chunk i's record copy on the copy stream and
-// records ready[i]; the compute stream waits for that event, widens 24-byte
-// records (lc_check32), and runs the version-order (or fused) pass over the
-// chunk's keys while the copy engine moves the next chunk.  (A pageable copy
-// may block the issuing thread until it has landed; issuing each chunk's
-// copy right before its kernels keeps the overlap either way.)
-struct Chunks {
-  int n = 0;
-  std::vector<int64_t> k;   // key boundaries, n + 1, local to the device's range
-  std::vector<int64_t> r;   // record offsets of those keys from the range's first record
-  std::function<int(int)> issue;
-  const hipEvent_t *ready = nullptr;
-  const lc_op32 *d_ops32 = nullptr;  // staging records to widen into d_ops (null: 48-byte copies)
-  const lc_op16 *d_ops16 = nullptr;  // (lc_check16) the same for 16-byte records
-  const int64_t *d_base = nullptr;   // key bases for the widening (null: 0)
-  int64_t max_len = 0;               // longest key (records)
-};
-// Chunks of kChunkBytes, the last ones halving down to kChunkTail: the
-// compute stream's tail after the last copy is one small chunk's widening and
-// version-order pass.  (Measured on C2's 240 MB of 24-byte records: 10
-// chunks of 24 MB 4.66 ms per call, 0.12 ms of it after the last copy; 29
-// chunks of 8 MB 5.2 ms — each pageable copy has a fixed cost.)
-constexpr size_t kChunkBytes = size_t(24) << 20;
-constexpr size_t kChunkTail = size_t(2) << 20;
-constexpr int kMaxChunks = 48;
-// A call whose pageable inputs and outputs fit in kStageMax bytes copies them
-// through the device's pinned staging buffer (a memcpy on the host, then a
-// DMA from pinned memory): the runtime's pageable path costs tens of
-// microseconds per copy, which small calls (C1, C4) pay in full.  At a few
-// MB the runtime's path is the faster one again (a 4.8 MB input staged:
-// 0.07-0.15 ms slower, profiles/r05/stage_ab.txt).
-constexpr size_t kStageMax = size_t(2) << 20;
 // The device's staging buffer (kStageMax bytes, allocated on first use), or
 // null with the context's error set.
-char *stage_buf(lc_ctx *c, Dev &d) {
+char *lcrt::stage_buf(lc_ctx *c, Dev &d) {
   if (!d.h_stage) {
     if (hipHostMalloc(reinterpret_cast<void **>(&d.h_stage), kStageMax, 0) != hipSuccess) {
       d.h_stage = nullptr;
@@ -197,31 +159,7 @@ char *stage_buf(lc_ctx *c, Dev &d) {
   return d.h_stage;
 }
 
-// Device-side lc_aux outputs of one run_device call (null: not wanted).
-struct AuxOut {
-  int32_t *wit = nullptr;   // per record, indexed like d_ops
-  int32_t *kind = nullptr;  // per key
-  int32_t *cert = nullptr;  // per key, 4 int32 (infeasibility certificates)
-  int32_t *cset = nullptr;  // per record (HALL position sets)
-  int64_t n_records = 0;
-};
-
-// Where a run_device call's records come from, beyond d_ops / d_off
-// (default: 48-byte records in place, offsets on the device only).
-struct Source {
-  // the shard's key offsets in host memory when the caller has them
-  // (lc_check_ex): the gap tier may then be launched early
-  const int64_t *h_off = nullptr;
-  // lc_check's chunked copies, or null: the records are in place
-  const Chunks *chunks = nullptr;
-  // the first pass over lc_op32 records (lc_check32 / lc_check_device32
-  // without lc_aux outputs): ops32 and the keys' bases (null: 0), indexed
-  // like d_ops / d_off; `widen` fills the 48-byte records the later tiers
-  // read (and names them) once a key is handed over
-  const lc_op32 *ops32 = nullptr;
-  const int64_t *base32 = nullptr;
-  std::function<int(const lc_op **)> widen;
-};
+namespace {
 
 // A gap-tier full-decision launch: its sizes and job (run_device).
 struct GapPlan {
@@ -233,9 +171,11 @@ struct GapPlan {
   lcdev::GapJob job{};
 };
 
+}  // namespace
+
 // Infeasibility certificates for the invalid keys of a run_device call
 // (cert.hip), after every tier has decided.
-int run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
+int lcrt::run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
                      const lcdev::KParams &p, const lc_key_result *d_out, hipStream_t st,
                      const AuxOut &wo) {
   if (!wo.cert || !wo.cset || n_keys <= 0) return 0;
@@ -252,8 +192,6 @@ int run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off
   return 0;
 }
 
-}  // namespace
-
 // A fused call's lazily copied status (Dev::st_pending): choose the next
 // call's pass from it and return the keys the crash-light decision took (the
 // call's n_gap), or -1 when nothing was pending.
@@ -265,13 +203,12 @@ int64_t lcrt::settle_status(Dev &d) {
   d.use_fused = 4 * (int64_t)n_light > d.st_keys;
   return n_light;
 }
-namespace {
 
 // A call that returned on the completion signal: its pass's HIP-event time,
 // read once the kernel has retired (now, if it has not yet), into the
 // device's statistics and the context's totals.  Before the events are
 // recorded again, and by lc_last_stats / lc_last_totals.
-void settle_timing(lc_ctx *c, Dev &d) {
+void lcrt::settle_timing(lc_ctx *c, Dev &d) {
   if (!d.timing_pending) return;
   d.timing_pending = false;
   float ms = 0;
@@ -285,11 +222,13 @@ void settle_timing(lc_ctx *c, Dev &d) {
 }
 
 // d_status copied into h_status, and waited for.
-int read_status(lc_ctx *c, Dev &d, hipStream_t st) {
+int lcrt::read_status(lc_ctx *c, Dev &d, hipStream_t st) {
   HIP_TRY(c, hipMemcpyAsync(d.h_status, d.d_status, sizeof(lcdev::KStatus), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   return 0;
 }
+
+namespace {
 
 // Wait for the pass's follower signal (seq in *h_done): spin, checking the
 // stream every 1,024 rounds; past 2 ms (or once the stream is idle, which
@@ -1179,10 +1118,12 @@ int end_call(Run &r) {
   return 0;
 }
 
+}  // namespace
+
 // Run the tiers for n_keys keys whose device arrays are in place.
-int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
-               const lcdev::KParams &p, lc_key_result *d_out, hipStream_t st, int64_t flags,
-               const AuxOut &ao = AuxOut(), const Source &src = Source()) {
+int lcrt::run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
+                     const lcdev::KParams &p, lc_key_result *d_out, hipStream_t st, int64_t flags,
+                     const AuxOut &ao, const Source &src) {
   Run r{c, d, d_ops, d_off, n_keys, p, d_out, st, flags, ao, src};
   r.fast_on = !(flags & LC_FLAG_NO_FAST_PATH);
   r.gap_on = !(flags & (LC_FLAG_NO_FAST_PATH | LC_FLAG_NO_GAP_TIER));
@@ -1219,347 +1160,9 @@ int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int6
   return counted_witness_stage(r);
 }
 
-
-// LC_FLAG_WHOLE_GPU: keys the tiers left :unknown at the configuration
-// budget (one workgroup's HBM sets were not enough) are searched again by the
-// frontier exchange (include/lincheck_fx.h), whose budget bounds each
-// return's configuration sets, as the oracle's does; its result replaces the
-// tiers' (verdict, fail op, explored, frontier).  fetch(k, records) and
-// store(k, result) move a key between the caller's memory (host or device)
-// and the engine.
-//
-// * Fewer such keys than the context has GPUs: each key's search spans every
-//   GPU of the context — one rank per GPU over RCCL (lc_fx_open_devices),
-//   the frontier partitioned by hash owner while it is large.
-//   Device contexts that share one GPU (LC_VIRTUAL_DEVICES) run their ranks
-//   in process instead (RCCL refuses two ranks on one device).
-// * Otherwise keys are independent (register.clj:108): up to kFxEngines
-//   single-GPU engines per GPU search different keys at once (one key's
-//   levels are latency-bound, so concurrent searches fill a GPU the way one
-//   cannot), as many as the GPU's free memory holds.
-//
-// Keys left :unknown because more than LC_MAX_WINDOW ops were open at once
-// (crashed writes/CAS pile up in the tiers' windows) are searched again too,
-// the same way: there the crashed ops of a key are counted per class instead
-// of holding a window slot each (fx.hip, "Counted classes"; owner_of hashes a
-// class by its absolute count, so the multi-GPU engine partitions them too).
-//
-// A failure of the re-search (an allocation, say) is this key's alone: it
-// keeps the tiers' :unknown, the error text goes to lc_last_error, and the
-// call still succeeds — as jepsen.independent loses only the key whose check
-// throws.
-int whole_gpu(lc_ctx *c, const std::vector<int64_t> &todo, const lc_opts *opts,
-              const std::function<int(int64_t, std::vector<lc_op> &)> &fetch,
-              const std::function<int(int64_t, const lc_key_result &)> &store) {
-  if (todo.empty()) return 0;
-  std::vector<int> ids;  // the context's distinct GPUs
-  for (const Dev &d : c->devs)
-    if (std::find(ids.begin(), ids.end(), d.id) == ids.end()) ids.push_back(d.id);
-  const int nranks = (int)c->devs.size();
-  std::atomic<int> failed{0};
-  auto note = [&](int64_t k, const std::string &what) {
-    failed++;
-    set_err(c, "LC_FLAG_WHOLE_GPU: key " + std::to_string(k) + " kept :unknown: " + what);
-  };
-  if (nranks > 1 && todo.size() < (size_t)nranks) {
-    if (!c->fx_all && !c->fx_all_failed) {
-      lc_fx_params fp{};
-      fp.part_above = -1;
-      fp.repl_below = -1;
-      int e;
-      if ((int)ids.size() == nranks) {
-        e = lc_fx_open_devices(&fp, ids.data(), (int32_t)ids.size(), &c->fx_all);
-      } else {
-        fp.device = ids[0];
-        fp.virtual_ranks = nranks;
-        e = lc_fx_open(&fp, nullptr, &c->fx_all);
-      }
-      if (e) {
-        c->fx_all = nullptr;
-        c->fx_all_failed = true;  // (e.g. no librccl) the single-GPU engines below take over
-        set_err(c, "LC_FLAG_WHOLE_GPU: multi-GPU frontier exchange unavailable (" +
-                       std::to_string(e) + "); searching keys one GPU each");
-      }
-    }
-    if (c->fx_all) {
-      std::vector<lc_op> recs;
-      for (int64_t k : todo) {
-        if (int x = fetch(k, recs)) return x;
-        lc_key_result r;
-        if (int x = lc_fx_check(c->fx_all, recs.data(), (int64_t)recs.size(), opts, &r)) {
-          note(k, std::string("lc_fx_check: ") + lc_fx_last_error(c->fx_all) + " (" +
-                      std::to_string(x) + ")");
-          continue;
-        }
-        if (int x = store(k, r)) return x;
-      }
-      return 0;
-    }
-  }
-  // key-parallel: engines per GPU, bounded by its free memory (lists and
-  // tables take up to ~352 B per configuration of the budget, two one-word table sets included)
-  const int64_t budget = opts && opts->max_configs_per_key > 0 ? opts->max_configs_per_key
-                                                                : kDefaultBudget;
-  const double per_engine = 352.0 * (double)(budget + 1) + (64 << 20);
-  for (int id : ids) {
-    int have = 0;
-    for (const auto &e : c->fxs) have += e.second == id;
-    size_t fr = 0, tot = 0;
-    (void)hipSetDevice(id);
-    int want = (int)kFxEngines;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-      want = (int)std::max<double>(1.0, std::min<double>(want, 0.8 * (double)fr / per_engine + have));
-    const int per_dev = (int)std::min<size_t>((size_t)want, (todo.size() + ids.size() - 1) / ids.size());
-    for (; have < per_dev; have++) {
-      lc_fx_params fp{};
-      fp.device = id;
-      fp.virtual_ranks = 1;
-      fp.part_above = -1;
-      fp.repl_below = -1;
-      lc_fx *f = nullptr;
-      if (int e = lc_fx_open(&fp, nullptr, &f)) {
-        set_err(c, "LC_FLAG_WHOLE_GPU: lc_fx_open failed (" + std::to_string(e) + ")");
-        break;
-      }
-      c->fxs.emplace_back(f, id);
-    }
-  }
-  const int ne = (int)c->fxs.size();
-  if (ne == 0) {
-    for (int64_t k : todo) note(k, "no frontier-exchange engine could be opened");
-    return 0;
-  }
-  std::atomic<size_t> next{0};
-  std::vector<int> erc(ne, 0);
-  auto run = [&](int e) {
-    (void)hipSetDevice(c->fxs[e].second);
-    std::vector<lc_op> recs;
-    for (;;) {
-      const size_t i = next.fetch_add(1);
-      if (i >= todo.size()) break;
-      const int64_t k = todo[i];
-      lc_key_result r;
-      if ((erc[e] = fetch(k, recs))) break;
-      if (int x = lc_fx_check(c->fxs[e].first, recs.data(), (int64_t)recs.size(), opts, &r)) {
-        note(k, std::string("lc_fx_check: ") + lc_fx_last_error(c->fxs[e].first) + " (" +
-                    std::to_string(x) + ")");
-        continue;
-      }
-      if ((erc[e] = store(k, r))) break;
-    }
-  };
-  std::vector<std::thread> th;
-  for (int e = 0; e < std::min<int>(ne, (int)todo.size()); e++) th.emplace_back(run, e);
-  for (auto &t : th) t.join();
-  for (int e = 0; e < ne; e++)
-    if (erc[e]) return erc[e];
-  return 0;
-}
-
-// Per-key device cost in record-scan units.  The tier a key
-// lands in follows from its records alone (check_kernel.hip, fast_key):
-//   * version-order tier (every :ok mutation versioned, nothing crashed):
-//     one pass over the records, cost n;
-//   * gap tier (crashed writes/CAS, versions pinned): two skeleton passes,
-//     the matching and, for an invalid key, the bisection; measured ~6x the
-//     fast tier per record on C2 with 5 % crashed ops (crash_leg), plus the
-//     matching's share, which grows with the crashed ops;
-//   * frontier search (an :ok mutation or a read [nil x] without a version):
-//     the frontier grows with the open window w; measured (model_leg,
-//     tools/frontier_dist.py) ~1,600x the fast tier per record at
-//     concurrency 10 and ~4,700x at 20, i.e. ~12 w^2, and crashed ops
-//     multiply the configurations (capped: the search's budget bounds it).
-// Plus a fixed 64 per key (launch share, result write).
-// (Records of either width: lc_op, or lc_op32 with LC_INF32 for LC_INF.)
-inline bool rec_crashed(const lc_op32 &o) { return o.ret == LC_INF32; }
-inline int64_t rec_call(const lc_op &o) { return o.call; }
-inline int64_t rec_call(const lc_op32 &o) { return (int64_t)o.call; }
-inline int64_t rec_ret(const lc_op &o) { return o.ret; }
-inline int64_t rec_ret(const lc_op32 &o) { return o.ret == LC_INF32 ? LC_INF : (int64_t)o.ret; }
-// a crashed write/CAS, or an :ok op without a version that the version order
-// cannot pin (a mutation, or a read of a value)
-template <class Op>
-inline void rec_kind(const Op &o, bool *crashed_mut, bool *unpinned) {
-  const bool mut = o.f == LC_F_WRITE || o.f == LC_F_CAS;
-  *crashed_mut = mut && rec_crashed(o);
-  *unpinned = !rec_crashed(o) && o.version == (int32_t)LC_NIL &&
-              (mut || (o.f == LC_F_READ && o.value != (int32_t)LC_NIL));
-}
-inline void rec_kind(const lc_op &o, bool *crashed_mut, bool *unpinned) {
-  const bool mut = o.f == LC_F_WRITE || o.f == LC_F_CAS;
-  *crashed_mut = mut && o.ret == LC_INF;
-  *unpinned = o.ret != LC_INF && o.version == LC_NIL &&
-              (mut || (o.f == LC_F_READ && o.value != LC_NIL));
-}
-
-// An lc_op16 record as the lc_op32 it stands for (include/lincheck.h)
-inline lc_op32 as32(const lc_op16 &q) {
-  const uint32_t v = q.fve >> 15 & 0x7FFFu, x = q.fve & 0x7FFFu;
-  return lc_op32{(int32_t)(q.fve >> 30), v == 0x7FFFu ? -2 : (int32_t)v - 1,
-                 x == 0x7FFFu ? -2 : (int32_t)x - 1, q.version, q.call, q.ret};
-}
-inline int64_t rec_call(const lc_op16 &o) { return (int64_t)o.call; }
-inline int64_t rec_ret(const lc_op16 &o) { return o.ret == LC_INF32 ? LC_INF : (int64_t)o.ret; }
-inline void rec_kind(const lc_op16 &o, bool *crashed_mut, bool *unpinned) {
-  rec_kind(as32(o), crashed_mut, unpinned);
-}
-
-template <class Op>
-double key_cost(const Op *o, int64_t n) {
-  int64_t crashed = 0, unpinned = 0;
-  for (int64_t i = 0; i < n; i++) {
-    bool cm, un;
-    rec_kind(o[i], &cm, &un);
-    crashed += cm;
-    unpinned += un;
-  }
-  const double kOverhead = 64;
-  if (!unpinned && !crashed) return (double)n + kOverhead;
-  if (!unpinned) return (6.0 + 0.01 * (double)crashed) * (double)n + kOverhead;
-  // open window: the most ops called and not yet returned at once
-  std::vector<int64_t> rets;
-  rets.reserve((size_t)n);
-  for (int64_t i = 0; i < n; i++) rets.push_back(rec_ret(o[i]));
-  std::sort(rets.begin(), rets.end());
-  int64_t w = 0;
-  size_t j = 0;
-  for (int64_t i = 0; i < n; i++) {  // records are sorted by call
-    while (j < rets.size() && rets[j] < rec_call(o[i])) j++;
-    w = std::max<int64_t>(w, i + 1 - (int64_t)j);
-  }
-  const double blow = std::pow(2.0, (double)std::min<int64_t>(crashed, 12));
-  return (double)n * (1.0 + 12.0 * (double)w * (double)w) * blow + kOverhead;
-}
-
-
-// lc_check's own split over its devices: the same contiguous equal-cost cut
-// as lc_plan_partition, but a key is priced by all its records only when a
-// sample of them (every kSampleStride-th) shows it is not a clean
-// version-pinned key (a crashed write/CAS, an :ok op without a version);
-// otherwise it costs its record count, which is what lc_key_cost gives a
-// clean key.  And the sample itself is taken only when a first probe — the
-// same sample of every kKeyStride-th key — finds an irregular key: a batch
-// whose probe is clean is split by record count.  Pricing every record read
-// the whole batch on the host (480 MB for C2: several ms even on 16 threads)
-// before any copy could start; sampling every key still touched every page
-// (0.6-0.9 ms of a 5-ms call on the GPU box, tools/plan_probe.cpp); the
-// probe reads ~1/16 of them.  Only the split's balance, never a verdict,
-// depends on these estimates.
-constexpr int64_t kSampleStride = 64;
-constexpr int64_t kKeyStride = 16;
-template <class Op>
-bool irregular_sample(const Op *o, int64_t n) {
-  for (int64_t i = 0; i < n; i += kSampleStride) {
-    bool cm, un;
-    rec_kind(o[i], &cm, &un);
-    if (cm || un) return true;
-  }
-  return false;
-}
-
-// fn(k0, k1) over the keys [0, n_keys), cut into nth contiguous ranges with
-// a thread each (nth <= 1: on this thread).
-template <class F>
-void for_key_ranges(int64_t n_keys, int nth, F fn) {
-  if (nth <= 1) return fn(0, n_keys);
-  std::vector<std::thread> th;
-  for (int t = 0; t < nth; t++) th.emplace_back(fn, n_keys * t / nth, n_keys * (t + 1) / nth);
-  for (auto &x : th) x.join();
-}
-
-template <class Op>
-void plan_devices(const Op *ops, const int64_t *key_off, int64_t n_keys, int nd,
-                  int64_t *bounds) {
-  std::vector<double> pre((size_t)n_keys + 1, 0.0);
-  bool any = false;
-  for (int64_t k = 0; k < n_keys && !any; k += kKeyStride)
-    any = irregular_sample(ops + key_off[k], key_off[k + 1] - key_off[k]);
-  auto price = [&](int64_t k0, int64_t k1) {
-    for (int64_t k = k0; k < k1; k++) {
-      const Op *o = ops + key_off[k];
-      const int64_t n = key_off[k + 1] - key_off[k];
-      pre[(size_t)k + 1] = any && irregular_sample(o, n) ? key_cost(o, n) : (double)n + 64.0;
-    }
-  };
-  const int nth = any ? (int)std::min<int64_t>(16, std::max<int64_t>(1, n_keys >> 10)) : 1;
-  for_key_ranges(n_keys, nth, price);
-  for (int64_t k = 0; k < n_keys; k++) pre[(size_t)k + 1] += pre[(size_t)k];
-  const double total = pre[(size_t)n_keys];
-  bounds[0] = 0;
-  int64_t k = 0;
-  for (int p = 1; p < nd; p++) {
-    const double goal = total * p / nd;
-    while (k < n_keys && pre[(size_t)k] < goal) k++;
-    bounds[p] = k;
-  }
-  bounds[nd] = n_keys;
-}
-
-// An lc_op32 record as the lc_op it stands for (include/lincheck.h, ABI 4).
-inline lc_op widen_op(const lc_op &o, int64_t) { return o; }
-inline lc_op widen_op(const lc_op32 &o, int64_t base) {
-  return lc_op{o.f, o.value, o.expected, o.version, base + (int64_t)o.call,
-               o.ret == LC_INF32 ? LC_INF : base + (int64_t)o.ret};
-}
-inline lc_op widen_op(const lc_op16 &o, int64_t base) { return widen_op(as32(o), base); }
-
-// The chunks of nk keys with offsets off[0..nk], records of rec_bytes:
-// contiguous key ranges of about kChunkBytes of input records, the last ones
-// halving down to kChunkTail (cut at key boundaries).  Fills ch.n, ch.k, ch.r.
-void plan_chunks(const int64_t *off, int64_t nk, size_t rec_bytes, Chunks &ch) {
-  const int64_t r0 = off[0];
-  const size_t in_bytes = rec_bytes * (size_t)(off[nk] - r0);
-  std::vector<size_t> sizes;  // from the end of the range
-  size_t sum = 0;
-  for (size_t left = in_bytes, want = kChunkTail; left > 0 && (int)sizes.size() < kMaxChunks - 1;) {
-    const size_t take = std::min(left, want);
-    sizes.push_back(take);
-    sum += take;
-    left -= take;
-    want = std::min(kChunkBytes, 2 * want);
-  }
-  ch.k.assign(1, 0);
-  int64_t rec_goal = (int64_t)((in_bytes - sum) / rec_bytes);  // records before the next cut
-  for (size_t i = sizes.size(); i-- > 1;) {
-    rec_goal += (int64_t)(sizes[i] / rec_bytes);
-    const int64_t k = std::lower_bound(off, off + nk, r0 + rec_goal) - off;
-    if (k > ch.k.back() && k < nk) ch.k.push_back(k);
-  }
-  ch.k.push_back(nk);
-  ch.n = (int)ch.k.size() - 1;
-  ch.r.clear();
-  for (int64_t k : ch.k) ch.r.push_back(off[k] - r0);
-}
-
-// A call's outputs back to the host: straight into the caller's buffers, or
-// (stage non-null) into the pinned buffer and copied out once the stream is
-// done.
-struct OutCopy {
-  void *to;
-  const void *from;
-  size_t bytes;
-};
-hipError_t copy_outputs(const OutCopy *oc, int n, hipStream_t st, char *stage) {
-  hipError_t e = hipSuccess;
-  size_t so = 0;
-  for (int i = 0; i < n && e == hipSuccess; i++) {
-    void *to = stage ? stage + so : oc[i].to;
-    so += up256(oc[i].bytes);
-    e = hipMemcpyAsync(to, oc[i].from, oc[i].bytes, hipMemcpyDeviceToHost, st);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess || !stage) return e;
-  so = 0;
-  for (int i = 0; i < n; i++) {
-    std::memcpy(oc[i].to, stage + so, oc[i].bytes);
-    so += up256(oc[i].bytes);
-  }
-  return e;
-}
-
 // One device's counters of the call added to the context's (zeroed when the
 // call began).
-void fill_stats(lc_stats &s, const Dev &d) {
+void lcrt::fill_stats(lc_stats &s, const Dev &d) {
   s.kernel_ms += d.kernel_ms;
   s.fast_kernel_ms += d.fast_ms;
   s.jit_kernel_ms += d.jit_ms;
@@ -1571,347 +1174,7 @@ void fill_stats(lc_stats &s, const Dev &d) {
   s.n_malformed += d.malformed;
 }
 
-// LC_FLAG_WHOLE_GPU: the keys the tiers left :unknown at the configuration
-// budget, and those with more than LC_MAX_WINDOW ops open at once.
-void unknown_keys(const lc_key_result *res, int64_t n_keys, std::vector<int64_t> &budget,
-                  std::vector<int64_t> &window) {
-  for (int64_t k = 0; k < n_keys; k++)
-    if (res[k].verdict == LC_UNKNOWN && res[k].reason == LC_REASON_CONFIG_BUDGET) budget.push_back(k);
-    else if (res[k].verdict == LC_UNKNOWN && res[k].reason == LC_REASON_WINDOW_OVERFLOW)
-      window.push_back(k);
-}
-
-// lc_check_ex (48-byte lc_op) and lc_check32 (24-byte lc_op32, ABI 4) from
-// host memory: the keys split over the context's devices (plan_devices), one
-// host thread per device.  Per device, the key offsets (and lc_check32's key
-// bases) are copied first, then the records in chunks of about kChunkBytes
-// on the device's copy stream; the compute stream decides each chunk's keys
-// with the version-order (or fused) pass as soon as the chunk has landed
-// (run_device, Chunks), widening 24-byte records on the way, so the PCIe
-// copy of chunk i + 1 overlaps the kernels of chunk i.  The later tiers run
-// over the whole range once every chunk is in.  Results and lc_aux outputs
-// are copied back into the caller's arrays.  Per call, lc_call_profile keeps
-// where the host wall time went.
-template <class Op>
-int check_host(lc_ctx *c, const Op *ops, const int64_t *key_off, const int64_t *key_base,
-               int64_t n_keys, const lc_opts *opts, lc_key_result *out, const lc_aux *aux) {
-  constexpr bool k32 = sizeof(Op) == sizeof(lc_op32);
-  constexpr bool k16 = sizeof(Op) == sizeof(lc_op16);
-  constexpr bool narrow = k32 || k16;  // records widened on the device, key bases
-  const auto t0 = std::chrono::steady_clock::now();
-  auto since = [&t0]() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  };
-  c->stats = lc_stats{};
-  c->prof = lc_call_profile{};
-  for (Dev &d : c->devs) {  // (a device without keys runs nothing)
-    d.counted = lc_counted_stats{};
-    d.wit = lc_witness_stats{};
-    d.cwit = lc_counted_witness_stats{};
-  }
-  if (n_keys < 0 || (n_keys > 0 && (!ops || !key_off || !out))) {
-    set_err(c, "lc_check: null buffer or negative n_keys");
-    return -EINVAL;
-  }
-  if (n_keys == 0) return 0;
-  if (key_off[0] < 0) {
-    set_err(c, "lc_check: key_off[0] < 0");
-    return -EINVAL;
-  }
-  for (int64_t k = 0; k < n_keys; k++)
-    if (key_off[k + 1] < key_off[k]) {
-      set_err(c, "lc_check: key_off not monotone at key " + std::to_string(k));
-      return -EINVAL;
-    }
-  lcdev::KParams p;
-  int rc = opts_to_params(c, opts, &p);
-  if (rc) return rc;
-  const int64_t flags = opts ? opts->flags : 0;
-  const bool want_wit = aux && aux->witness && aux->witness_kind;
-  const bool want_cert = aux && aux->certificate;
-  const int nd = (int)c->devs.size();
-  c->prof.checked_ms = since();
-  std::vector<int64_t> bounds(nd + 1);
-  if (nd > 1) plan_devices(ops, key_off, n_keys, nd, bounds.data());
-  else bounds[0] = 0, bounds[1] = n_keys;
-  c->prof.planned_ms = since();
-  // the longest key (the widening's grid); C4's 5,000-op key takes more
-  // workgroups than a C2 key
-  int64_t max_len = 0;
-  if (narrow)
-    for (int64_t k = 0; k < n_keys; k++) max_len = std::max(max_len, key_off[k + 1] - key_off[k]);
-
-  std::vector<int> rcs(nd, 0);
-  std::vector<int> nchunks(nd, 0);
-  auto work = [&](int di) {
-    Dev &d = c->devs[di];
-    d.t_start = since();
-    d.t_end = d.t_start;
-    const int64_t a = bounds[di], b = bounds[di + 1];
-    const int64_t nk = b - a;
-    const auto tw = std::chrono::steady_clock::now();
-    d.last = lc_device_stats{};
-    d.last.device = d.id;
-    d.last.key_begin = a;
-    d.last.key_end = b;
-    d.kernel_ms = 0;
-    if (nk <= 0) return;
-    if (hipSetDevice(d.id) != hipSuccess) {
-      rcs[di] = -EIO;
-      return;
-    }
-    const int64_t r0 = key_off[a], r1 = key_off[b];
-    const int64_t nrec = r1 - r0;
-    const size_t ops_bytes = sizeof(lc_op) * (size_t)nrec;  // on the device: 48-byte records
-    const size_t in_bytes = sizeof(Op) * (size_t)nrec;      // what crosses PCIe
-    int r = ensure(c, d.d_ops, ops_bytes);
-    // (the narrow records' staging: d_ops32, whichever width)
-    if (!r && narrow) r = ensure(c, d.d_ops32, in_bytes);
-    if (!r && narrow && key_base) r = ensure(c, d.d_base, sizeof(int64_t) * (size_t)nk);
-    if (!r) r = ensure(c, d.d_off, sizeof(int64_t) * (size_t)(nk + 1));
-    if (!r) r = ensure(c, d.d_out, sizeof(lc_key_result) * (size_t)nk);
-    if (!r && want_wit) r = ensure(c, d.d_wit, sizeof(int32_t) * (size_t)nrec);
-    if (!r && want_wit) r = ensure(c, d.d_kind, sizeof(int32_t) * (size_t)nk);
-    if (!r && want_cert) r = ensure(c, d.d_cert, 4 * sizeof(int32_t) * (size_t)nk);
-    if (!r && want_cert) r = ensure(c, d.d_cset, sizeof(int32_t) * (size_t)nrec);
-    if (r) {
-      rcs[di] = r;
-      return;
-    }
-    // small pageable calls: inputs (offsets, bases, records) and outputs
-    // (results, lc_aux arrays) through the pinned staging buffer
-    auto up = up256;
-    const bool pinned = is_pinned(c, ops + r0, in_bytes);
-    const size_t off_bytes = sizeof(int64_t) * (size_t)(nk + 1);
-    const size_t base_bytes = narrow && key_base ? sizeof(int64_t) * (size_t)nk : 0;
-    const size_t out_bytes =
-        up(sizeof(lc_key_result) * (size_t)nk) +
-        (want_wit ? up(sizeof(int32_t) * (size_t)nrec) + up(sizeof(int32_t) * (size_t)nk) : 0) +
-        (want_cert ? up(4 * sizeof(int32_t) * (size_t)nk) + up(sizeof(int32_t) * (size_t)nrec) : 0);
-    const size_t stage_need = up(off_bytes) + up(base_bytes) + up(in_bytes) + out_bytes;
-    // (not with lc_aux outputs: the drop-in's C5 call with witnesses and
-    // certificates measured 0.05-0.1 ms slower staged)
-    const bool stage = !pinned && !want_wit && !want_cert && stage_need <= kStageMax;
-    if (stage && !stage_buf(c, d)) {
-      rcs[di] = -ENOMEM;
-      return;
-    }
-    char *st_off = stage ? d.h_stage : nullptr;
-    char *st_base = stage ? st_off + up(off_bytes) : nullptr;
-    char *st_ops = stage ? st_base + up(base_bytes) : nullptr;
-    char *st_out = stage ? st_ops + up(in_bytes) : nullptr;
-    Chunks ch;
-    plan_chunks(key_off + a, nk, sizeof(Op), ch);
-    while ((int)d.cev.size() < ch.n) {
-      hipEvent_t e = nullptr;
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-        set_err(c, "hipEventCreateWithFlags failed");
-        rcs[di] = -EIO;
-        return;
-      }
-      d.cev.push_back(e);
-    }
-    ch.ready = d.cev.data();
-    ch.max_len = max_len;
-    if (k32) ch.d_ops32 = reinterpret_cast<const lc_op32 *>(d.d_ops32.p);
-    if (k16) ch.d_ops16 = reinterpret_cast<const lc_op16 *>(d.d_ops32.p);
-    if (narrow) ch.d_base = key_base ? d.d_base.p : nullptr;
-    nchunks[di] = ch.n;
-    char *dst = narrow ? d.d_ops32.p : reinterpret_cast<char *>(d.d_ops.p);
-    const char *src = reinterpret_cast<const char *>(ops + r0);
-    // the key offsets (and bases) lead; the compute stream waits for the
-    // first chunk's event, which follows them on the copy stream
-    hipError_t e = hipEventRecord(d.eh0, d.cst);
-    const void *src_off = key_off + a, *src_base = narrow && key_base ? key_base + a : nullptr;
-    if (stage) {
-      std::memcpy(st_off, src_off, off_bytes);
-      if (base_bytes) std::memcpy(st_base, src_base, base_bytes);
-      src_off = st_off;
-      src_base = st_base;
-    }
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(d.d_off.p, src_off, off_bytes, hipMemcpyHostToDevice, d.cst);
-    if (e == hipSuccess && base_bytes)
-      e = hipMemcpyAsync(d.d_base.p, src_base, base_bytes, hipMemcpyHostToDevice, d.cst);
-    if (e != hipSuccess) {
-      set_err(c, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e));
-      rcs[di] = -EIO;
-      return;
-    }
-    // the second copy stream starts behind the offsets too
-    if (e == hipSuccess) e = hipEventRecord(d.cev[0], d.cst);
-    if (e == hipSuccess) e = hipStreamWaitEvent(d.cst2, d.cev[0], 0);
-    if (e != hipSuccess) {
-      set_err(c, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e));
-      rcs[di] = -EIO;
-      return;
-    }
-    // Two copy streams, chunks alternating, the odd ones issued by a helper
-    // thread: a copy call returns only once the runtime has staged (pageable)
-    // or queued it, so one issuing thread left the link idle between copies —
-    // two device contexts copying at once moved 57 GB/s against 52-53 for one
-    // thread (tools/host32_probe.py)
-    auto copy = [&](int i) -> hipError_t {
-      const size_t o = sizeof(Op) * (size_t)ch.r[i];
-      const size_t bytes = sizeof(Op) * (size_t)(ch.r[i + 1] - ch.r[i]);
-      hipStream_t cs = i % 2 ? d.cst2 : d.cst;
-      const char *from = src + o;
-      if (stage && bytes) {
-        std::memcpy(st_ops + o, from, bytes);
-        from = st_ops + o;
-      }
-      hipError_t x = bytes ? hipMemcpyAsync(dst + o, from, bytes, hipMemcpyHostToDevice, cs)
-                           : hipSuccess;
-      if (x == hipSuccess) x = hipEventRecord(d.cev[(size_t)i], cs);
-      return x;
-    };
-    std::vector<std::atomic<int>> issued((size_t)ch.n);  // odd chunks: 1 issued, -1 failed
-    for (auto &f : issued) f.store(0);
-    std::atomic<bool> stop{false};
-    std::thread helper;
-    if (ch.n >= 4)
-      helper = std::thread([&] {
-        (void)hipSetDevice(d.id);
-        for (int i = 1; i < ch.n && !stop.load(std::memory_order_relaxed); i += 2)
-          issued[(size_t)i].store(copy(i) == hipSuccess ? 1 : -1, std::memory_order_release);
-      });
-    ch.issue = [&](int i) -> int {
-      hipError_t x = hipSuccess;
-      if (i % 2 == 0 || !helper.joinable()) {
-        x = copy(i);
-      } else {
-        int f;
-        while ((f = issued[(size_t)i].load(std::memory_order_acquire)) == 0) std::this_thread::yield();
-        if (f < 0) x = hipErrorUnknown;
-      }
-      if (x == hipSuccess && i == ch.n - 1) {
-        // both copy streams done
-        if (ch.n > 1) x = hipStreamWaitEvent(d.cst, d.cev[(size_t)i - 1], 0);
-        if (x == hipSuccess) x = hipStreamWaitEvent(d.cst, d.cev[(size_t)i], 0);
-        if (x == hipSuccess) x = hipEventRecord(d.eh1, d.cst);
-      }
-      if (x != hipSuccess) {
-        set_err(c, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(x));
-        return -EIO;
-      }
-      return 0;
-    };
-    auto join_helper = [&] {
-      stop.store(true);
-      if (helper.joinable()) helper.join();
-    };
-    d.last.h2d_bytes = (int64_t)(in_bytes + sizeof(int64_t) * (size_t)(nk + 1) +
-                                 (narrow && key_base ? sizeof(int64_t) * (size_t)nk : 0));
-    d.last.pinned = pinned;
-    AuxOut ao;
-    ao.n_records = nrec;
-    if (want_wit) {
-      ao.wit = d.d_wit.p;
-      ao.kind = d.d_kind.p;
-    }
-    if (want_cert) {
-      ao.cert = d.d_cert.p;
-      ao.cset = d.d_cset.p;
-    }
-    Source from;
-    from.h_off = key_off + a;
-    from.chunks = &ch;
-    if (k32 && !want_wit && !want_cert && !(flags & LC_FLAG_NO_FAST_PATH)) {
-      // decided from the 24-byte records; widened only if a key is handed over
-      from.ops32 = ch.d_ops32;
-      from.base32 = ch.d_base;
-      from.widen = [&](const lc_op **out) -> int {
-        HIP_TRY(c, lcdev::launch_widen32(ch.d_ops32, d.d_off.p, ch.d_base, nk, max_len, d.d_ops.p,
-                                         d.stream));
-        *out = d.d_ops.p;
-        return 0;
-      };
-    }
-    r = run_device(c, d, d.d_ops.p, d.d_off.p, nk, p, d.d_out.p, d.stream, flags, ao, from);
-    join_helper();
-    if (!r) r = run_certificates(c, d, d.d_ops.p, d.d_off.p, nk, p, d.d_out.p, d.stream, ao);
-    if (r) {
-      // the copy stream may still read the caller's buffer
-      (void)hipStreamSynchronize(d.cst);
-      (void)hipStreamSynchronize(d.cst2);
-      rcs[di] = r;
-      return;
-    }
-    OutCopy oc[5];
-    int n_oc = 0;
-    oc[n_oc++] = {out + a, d.d_out.p, sizeof(lc_key_result) * (size_t)nk};
-    if (want_wit && nrec) oc[n_oc++] = {aux->witness + r0, d.d_wit.p, sizeof(int32_t) * (size_t)nrec};
-    if (want_wit) oc[n_oc++] = {aux->witness_kind + a, d.d_kind.p, sizeof(int32_t) * (size_t)nk};
-    if (want_cert) oc[n_oc++] = {aux->certificate + 4 * a, d.d_cert.p, 4 * sizeof(int32_t) * (size_t)nk};
-    if (want_cert && aux->certificate_set && nrec)
-      oc[n_oc++] = {aux->certificate_set + r0, d.d_cset.p, sizeof(int32_t) * (size_t)nrec};
-    e = copy_outputs(oc, n_oc, d.stream, st_out);
-    if (e != hipSuccess) {
-      set_err(c, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e));
-      rcs[di] = -EIO;
-      return;
-    }
-    // eh1 follows the last copy on the copy stream, which the compute stream
-    // waited for by the chunk's own event: it may complete a moment after the
-    // stream synchronised above (several device threads on one GPU), and an
-    // elapsed time read before then fails (h2d_ms would read 0)
-    float hms = 0;
-    if (hipEventSynchronize(d.eh1) == hipSuccess &&
-        hipEventElapsedTime(&hms, d.eh0, d.eh1) == hipSuccess)
-      d.last.h2d_ms = hms;
-    d.last.kernel_ms = d.kernel_ms;
-    d.last.total_ms = std::chrono::duration<double, std::milli>(
-                          std::chrono::steady_clock::now() - tw).count();
-    d.t_end = since();
-  };
-  if (nd == 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> th;
-    for (int di = 0; di < nd; di++) th.emplace_back(work, di);
-    for (auto &t : th) t.join();
-  }
-  c->prof.first_start_ms = c->prof.first_end_ms = 1e300;
-  for (int di = 0; di < nd; di++) {
-    const Dev &d = c->devs[di];
-    if (rcs[di] && !rc) rc = rcs[di];
-    fill_stats(c->stats, d);
-    c->prof.first_start_ms = std::min(c->prof.first_start_ms, d.t_start);
-    c->prof.last_start_ms = std::max(c->prof.last_start_ms, d.t_start);
-    c->prof.first_end_ms = std::min(c->prof.first_end_ms, d.t_end);
-    c->prof.last_end_ms = std::max(c->prof.last_end_ms, d.t_end);
-    c->prof.n_chunks += nchunks[di];
-  }
-  c->prof.joined_ms = since();
-  if (!rc && (flags & LC_FLAG_WHOLE_GPU)) {
-    std::vector<int64_t> todo, todo_w;
-    unknown_keys(out, n_keys, todo, todo_w);
-    auto fetch = [&](int64_t k, std::vector<lc_op> &v) {
-      v.resize((size_t)(key_off[k + 1] - key_off[k]));
-      const int64_t base = key_base ? key_base[k] : 0;
-      for (size_t i = 0; i < v.size(); i++) v[i] = widen_op(ops[key_off[k] + (int64_t)i], base);
-      return 0;
-    };
-    auto store = [&](int64_t k, const lc_key_result &r) {
-      out[k] = r;
-      // re-decided by the frontier exchange: no certificate (cert.hip covers
-      // the tiers' decisions)
-      if (want_cert)
-        for (int j = 0; j < 4; j++) aux->certificate[4 * k + j] = j == 0 ? LC_CERT_NONE : j < 3 ? -1 : 0;
-      return 0;
-    };
-    rc = whole_gpu(c, todo, opts, fetch, store);
-    if (!rc) rc = whole_gpu(c, todo_w, opts, fetch, store);
-  }
-  c->prof.whole_gpu_ms = since();
-  c->stats.n_keys = n_keys;
-  c->stats.n_ops = key_off[n_keys] - key_off[0];
-  c->stats.n_devices = nd;
-  c->stats.total_ms = since();
-  c->prof.total_ms = c->stats.total_ms;
-  c->prof.n_devices = nd;
-  return rc;
-}
+namespace {
 
 // key_off[n_keys] - key_off[0] of key offsets that live in device memory,
 // read through d.h_status (pinned).  Only before any status copy of the
@@ -1942,40 +1205,6 @@ int widen_device32(lc_ctx *c, Dev &d, const lc_op32 *d_ops32, const int64_t *d_k
   HIP_TRY(c, lcdev::launch_widen32(d_ops32, d_key_off, d_key_base, n_keys, 4 * (*nrec / n_keys + 1),
                                    d.d_ops.p, st));
   return 0;
-}
-
-// LC_FLAG_WHOLE_GPU after a device call: the results and the keys' records
-// are in device memory: read back the verdicts, and each key the frontier
-// exchange takes.  d_cert: the call's certificates (null: none wanted).
-int whole_gpu_device(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off, int64_t n_keys,
-                     const lc_opts *opts, lc_key_result *d_out, int32_t *d_cert, hipStream_t st) {
-  std::vector<lc_key_result> res((size_t)n_keys);
-  int64_t base = 0;
-  HIP_TRY(c, hipMemcpyAsync(res.data(), d_out, sizeof(lc_key_result) * (size_t)n_keys,
-                            hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(&base, d_key_off, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  std::vector<int64_t> todo, todo_w;
-  unknown_keys(res.data(), n_keys, todo, todo_w);
-  auto fetch = [&](int64_t k, std::vector<lc_op> &v) {
-    int64_t se[2];
-    if (hipMemcpy(se, d_key_off + k, sizeof se, hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
-    v.resize((size_t)(se[1] - se[0]));
-    if (!v.empty() && hipMemcpy(v.data(), d_ops + (se[0] - base), sizeof(lc_op) * v.size(),
-                                hipMemcpyDeviceToHost) != hipSuccess)
-      return -EIO;
-    return 0;
-  };
-  auto store = [&](int64_t k, const lc_key_result &r) {
-    if (d_cert) {
-      const int32_t none[4] = {LC_CERT_NONE, -1, -1, 0};
-      if (hipMemcpy(d_cert + 4 * k, none, sizeof none, hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-    }
-    return hipMemcpy(d_out + k, &r, sizeof r, hipMemcpyHostToDevice) == hipSuccess ? 0 : -EIO;
-  };
-  int rc = whole_gpu(c, todo, opts, fetch, store);
-  if (!rc) rc = whole_gpu(c, todo_w, opts, fetch, store);
-  return rc;
 }
 
 }  // namespace
@@ -2068,215 +1297,6 @@ int lcrt::check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, 
                           std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
-
-namespace {
-
-// The argument checks lc_check_frontiers and lc_check_frontiers_counted
-// share (`bad`: the call's own buffer and size test).
-int frontier_args(lc_ctx *c, const char *fn, bool bad, const int64_t *key_off, int64_t n_keys) {
-  const std::string name(fn);
-  if (bad) {
-    set_err(c, name + ": null buffer, negative n_keys or max_per_key < 1");
-    return -EINVAL;
-  }
-  if (n_keys == 0) return 0;
-  if (key_off[0] < 0) {
-    set_err(c, name + ": key_off[0] < 0");
-    return -EINVAL;
-  }
-  for (int64_t k = 0; k < n_keys; k++)
-    if (key_off[k + 1] < key_off[k]) {
-      set_err(c, name + ": key_off not monotone at key " + std::to_string(k));
-      return -EINVAL;
-    }
-  return 0;
-}
-
-// Their inputs on the context's first GPU: the records in d_ops, the offsets
-// and the stops in d_off (stops at d_off + n_keys + 1), through the staging
-// buffer when pageable and small (as lc_check's); d_status zeroed.  The
-// scratch is the context's lc_check buffers (a context is not re-entrant).
-int frontier_upload(lc_ctx *c, Dev &d, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
-                    const int64_t *stop_op) {
-  const int64_t r0 = key_off[0], nrec = key_off[n_keys] - r0;
-  int e = ensure(c, d.d_ops, sizeof(lc_op) * (size_t)nrec);
-  if (!e) e = ensure(c, d.d_off, sizeof(int64_t) * (size_t)(2 * n_keys + 1));
-  if (e) return e;
-  int64_t *d_off = d.d_off.p, *d_stop = d_off + (n_keys + 1);
-  hipStream_t st = d.stream;
-  const void *src_ops = ops + r0, *src_off = key_off, *src_stop = stop_op;
-  const size_t ops_b = sizeof(lc_op) * (size_t)nrec, off_b = sizeof(int64_t) * (size_t)(n_keys + 1),
-               stop_b = sizeof(int64_t) * (size_t)n_keys;
-  if (ops_b + off_b + stop_b + 512 <= kStageMax && !is_pinned(c, ops + r0, ops_b)) {
-    char *sb = stage_buf(c, d);
-    if (!sb) return -ENOMEM;
-    char *so = sb, *sf = so + up256(ops_b), *ss = sf + up256(off_b);
-    std::memcpy(so, src_ops, ops_b);
-    std::memcpy(sf, src_off, off_b);
-    std::memcpy(ss, src_stop, stop_b);
-    src_ops = so;
-    src_off = sf;
-    src_stop = ss;
-  }
-  HIP_TRY(c, hipMemcpyAsync(d.d_ops.p, src_ops, ops_b, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(d_off, src_off, off_b, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemcpyAsync(d_stop, src_stop, stop_b, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
-  d.status_dirty = true;
-  return 0;
-}
-
-// One key of lc_check_frontiers_counted on the host: whether the device may
-// search it, and each class's members (record indices, in record order).
-// The classes are lc_counted_plan's, cut as the device cuts them: a key with
-// a record the device reads as malformed (records.h decode) is left out, so
-// every field the classes compare is the same number on both sides.
-struct CountedKey {
-  bool take = false;
-  std::vector<std::vector<int32_t>> members;
-};
-
-CountedKey counted_classes_of(const lc_op *k, int64_t n, int64_t stop) {
-  CountedKey ck;
-  constexpr int64_t kFieldMax = 0x7FFFFFFE, kNever = 0xFFFFFFFFll;
-  if (n <= 0 || n > INT32_MAX || stop < 0 || stop >= n || k[stop].ret == LC_INF) return ck;
-  struct Cls {
-    int64_t f, value, expected, version;
-  };
-  std::vector<Cls> cls;
-  const int64_t base = k[0].call;
-  for (int64_t i = 0; i < n; i++) {
-    const lc_op &o = k[i];
-    const int64_t rc = o.call - base, rr = o.ret - base;
-    if (o.value < -1 || o.value > kFieldMax || o.expected < -1 || o.expected > kFieldMax ||
-        o.call < 0 || o.ret <= o.call || rc < 0 || rc >= kNever || (o.ret != LC_INF && rr >= kNever))
-      return ck;
-    if ((o.f != LC_F_WRITE && o.f != LC_F_CAS) || o.ret != LC_INF) continue;
-    const int64_t ver = lccount::counted_version(o.version);
-    size_t ci = 0;
-    while (ci < cls.size() && !(cls[ci].f == o.f && cls[ci].value == o.value &&
-                                cls[ci].expected == o.expected && cls[ci].version == ver))
-      ci++;
-    if (ci == cls.size()) {
-      if (ci == (size_t)LC_COUNTED_MAX_CLASSES) return ck;
-      cls.push_back(Cls{o.f, o.value, o.expected, ver});
-      ck.members.emplace_back();
-    }
-    ck.members[ci].push_back((int32_t)i);
-  }
-  int bits = 0;
-  for (const auto &m : ck.members) bits += lccount::counted_width((int64_t)m.size());
-  const int ncls = (int)ck.members.size();
-  ck.take = lccount::counted_fits(ncls, lccount::counted_slots(bits, ncls));
-  return ck;
-}
-
-// lc_check_frontiers_counted behind its argument checks.
-int frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
-                      const int64_t *stop_op, const lcdev::KParams &p, lc_counted_config *out,
-                      int32_t max_per_key, int32_t *n_out, int64_t *n_total, int64_t *pending) {
-  const int64_t r0 = key_off[0];
-  // the keys the device may search (the others: -1)
-  std::vector<CountedKey> keys((size_t)n_keys);
-  std::vector<int32_t> list;
-  for (int64_t k = 0; k < n_keys; k++) {
-    n_out[k] = -1;
-    n_total[k] = -1;
-    keys[k] = counted_classes_of(ops + key_off[k], key_off[k + 1] - key_off[k], stop_op[k]);
-    if (keys[k].take) list.push_back((int32_t)k);
-  }
-  int32_t n_list = (int32_t)list.size();
-  if (n_list == 0) return 0;
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  (void)settle_status(d);  // a fused call's status copy may still be pending
-  // scratch: the compact configurations, then every key's tables, in d_gws
-  const size_t cfg_bytes = sizeof(lcdev::CountedCfg) * (size_t)max_per_key * (size_t)n_keys;
-  const size_t key_bytes = sizeof(lcdev::CountedKeyOut) * (size_t)n_keys;
-  int e = ensure(c, d.d_gws, cfg_bytes + key_bytes);
-  if (!e) e = ensure(c, d.d_jit, sizeof(int32_t) * (size_t)n_keys);
-  if (!e) e = ensure(c, d.d_jit2, sizeof(int32_t) * (size_t)n_keys);
-  if (!e) e = frontier_upload(c, d, ops, key_off, n_keys, stop_op);
-  if (e) return e;
-  int64_t *d_off = d.d_off.p, *d_stop = d_off + (n_keys + 1);
-  int32_t *d_list = d.d_jit.p, *d_next = d.d_jit2.p;
-  lcdev::CountedCfg *d_cfg = reinterpret_cast<lcdev::CountedCfg *>(d.d_gws.p);
-  lcdev::CountedKeyOut *d_key = reinterpret_cast<lcdev::CountedKeyOut *>(
-      reinterpret_cast<char *>(d.d_gws.p) + cfg_bytes);
-  hipStream_t st = d.stream;
-  HIP_TRY(c, hipMemcpyAsync(d_list, list.data(), sizeof(int32_t) * (size_t)n_list,
-                            hipMemcpyHostToDevice, st));
-  // counted_tier's ladder of set capacities
-  const int by_value = !env_is_off("LC_COUNTED_BY_VALUE");
-  for (int tier = 0; tier < kHbmTiers && n_list > 0; tier++) {
-    const int waves = std::min<int>(kHbmWaves[tier], n_list);
-    if ((e = ensure(c, d.d_ws, lcdev::hbm_tier_ws_bytes(waves, kHbmCap[tier])))) return e;
-    if (tier > 0) {
-      HIP_TRY(c, hipMemsetAsync(&d.d_status->n_overflow2, 0, sizeof(int32_t), st));
-      HIP_TRY(c, hipMemsetAsync(&d.d_status->hbm_next, 0, sizeof(int32_t), st));
-    }
-    HIP_TRY(c, lcdev::launch_counted_frontier(d.d_ops.p, d_off, d_stop, d_list, n_list, p, d.d_ws.p,
-                                              waves, kHbmCap[tier], d_cfg, max_per_key, d_key, d_next,
-                                              &d.d_status->n_overflow2, &d.d_status->hbm_next,
-                                              tier == kHbmTiers - 1, by_value, st));
-    if ((e = read_status(c, d, st))) return e;
-    n_list = tier < kHbmTiers - 1 ? d.h_status->n_overflow2 : 0;
-    std::swap(d_list, d_next);
-  }
-  std::vector<lcdev::CountedCfg> cfg((size_t)max_per_key * (size_t)n_keys);
-  std::vector<lcdev::CountedKeyOut> kout((size_t)n_keys);
-  HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
-  HIP_TRY(c, hipMemcpyAsync(cfg.data(), d_cfg, cfg_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(kout.data(), d_key, key_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  d.status_dirty = false;
-  // Expansion to record indices: the pending window slots through the key's
-  // slot table; of class c, members [linearized, called) — deadline order
-  // linearizes a class's crashed members in call order, which is record order.
-  std::vector<int64_t> pend;
-  for (const int32_t k : list) {
-    const lcdev::CountedKeyOut &ko = kout[k];
-    const CountedKey &ck = keys[k];
-    const int64_t n_k = key_off[k + 1] - key_off[k];
-    bool ok = ko.n >= -1 && ko.n <= max_per_key && ko.total >= ko.n &&
-              (ko.n <= 0 || ko.n_classes == (int32_t)ck.members.size());
-    for (int32_t j = 0; ok && j < ko.n; j++) {
-      const lcdev::CountedCfg &g = cfg[(size_t)k * max_per_key + j];
-      pend.clear();
-      uint64_t slots = g.word;
-      for (size_t ci = 0; ci < ck.members.size(); ci++) {
-        const uint64_t field = ((1ull << ko.width[ci]) - 1) << ko.shift[ci];
-        const int64_t lin = (int64_t)((g.word & field) >> ko.shift[ci]), called = ko.called[ci];
-        slots &= ~field;
-        ok = ok && lin <= called && called <= (int64_t)ck.members[ci].size();
-        for (int64_t m = lin; ok && m < called; m++) pend.push_back(ck.members[ci][m]);
-      }
-      for (; ok && slots; slots &= slots - 1) {
-        const int32_t rec = ko.slot_rec[__builtin_ctzll(slots)];
-        ok = rec >= 0 && rec < n_k;
-        pend.push_back(rec);
-      }
-      if (!ok) break;
-      std::sort(pend.begin(), pend.end());
-      lc_counted_config &o = out[(size_t)k * max_per_key + j];
-      o.version = g.version;
-      o.value = g.value;
-      o.n_pending = (int64_t)pend.size();
-      o.pending_at = (int64_t)max_per_key * (key_off[k] - r0) + (int64_t)j * n_k;
-      ok = o.n_pending <= n_k;
-      if (ok) std::copy(pend.begin(), pend.end(), pending + o.pending_at);
-    }
-    if (!ok) {  // (the device's tables and the host's classes disagree: a bug, not an input)
-      set_err(c, "lc_check_frontiers_counted: inconsistent frontier of key " + std::to_string(k));
-      return -EIO;
-    }
-    n_out[k] = ko.n;
-    n_total[k] = ko.total;
-  }
-  return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -2465,46 +1485,6 @@ int lc_last_counted_witness_stats(lc_ctx *c, lc_counted_witness_stats *out) {
   return 0;
 }
 
-int lc_counted_plan(const lc_op *ops, int64_t n, lc_counted_layout *out) {
-  if (!out || n < 0 || (n > 0 && !ops)) return -EINVAL;
-  *out = lc_counted_layout{};
-  struct Cls {
-    int64_t f, value, expected, version, members;
-  };
-  std::vector<Cls> cls;  // in order of first call (records are sorted by call)
-  for (int64_t i = 0; i < n; i++) {
-    const lc_op &o = ops[i];
-    if ((o.f != LC_F_WRITE && o.f != LC_F_CAS) || o.ret != LC_INF) continue;
-    const int64_t ver = lccount::counted_version(o.version);
-    auto it = std::find_if(cls.begin(), cls.end(), [&](const Cls &k) {
-      return k.f == o.f && k.value == o.value && k.expected == o.expected && k.version == ver;
-    });
-    if (it == cls.end()) cls.push_back(Cls{o.f, o.value, o.expected, ver, 1});
-    else it->members++;
-  }
-  int64_t bits = 0;
-  for (size_t k = 0; k < cls.size(); k++) {
-    const int w = lccount::counted_width(cls[k].members);
-    bits += w;
-    if (k < (size_t)LC_COUNTED_MAX_CLASSES) {
-      out->f[k] = cls[k].f;
-      out->value[k] = cls[k].value;
-      out->expected[k] = cls[k].expected;
-      out->version[k] = cls[k].version;
-      out->members[k] = cls[k].members;
-      out->width[k] = w;
-      out->shift[k] = (int32_t)(64 - bits);
-    }
-  }
-  const int64_t ncls = (int64_t)cls.size();
-  out->n_classes = (int32_t)std::min<int64_t>(ncls, INT32_MAX);
-  out->field_bits = (int32_t)std::min<int64_t>(bits, INT32_MAX);
-  // (beyond int: far from fitting either way)
-  out->slots = (int32_t)std::max<int64_t>(std::min(64 - bits, 64 - ncls), INT32_MIN);
-  out->fits = lccount::counted_fits(out->n_classes, out->slots);
-  return 0;
-}
-
 int lc_last_totals(lc_ctx *c, lc_totals *out, int32_t reset) {
   if (!c || !out) return -EINVAL;
   lc_totals t{};
@@ -2558,82 +1538,6 @@ int lc_host_unregister(lc_ctx *c, const void *ptr) {
   return -EINVAL;
 }
 
-int lc_key_cost(const lc_op *ops, const int64_t *key_off, int64_t n_keys, double *costs) {
-  if (!ops || !key_off || !costs || n_keys < 0) return -EINVAL;
-  for (int64_t k = 0; k < n_keys; k++) {
-    const int64_t n = key_off[k + 1] - key_off[k];
-    if (n < 0) return -EINVAL;
-    costs[k] = key_cost(ops + key_off[k], n);
-  }
-  return 0;
-}
-
-// Contiguous split at equal cost: boundary p is the first key whose cost
-// prefix reaches p/n_parts of the total (keys stay in order, so each device
-// gets one contiguous slice of the caller's arrays).
-int lc_plan_partition(const lc_op *ops, const int64_t *key_off, int64_t n_keys,
-                      int32_t n_parts, int64_t *bounds) {
-  if (!key_off || !bounds || n_parts < 1 || n_keys < 0) return -EINVAL;
-  for (int64_t k = 0; k < n_keys; k++)
-    if (key_off[k + 1] < key_off[k]) return -EINVAL;
-  std::vector<double> pre((size_t)n_keys + 1, 0.0);
-  // each key's cost reads its records once: 10M records (480 MB) is tens of
-  // ms on one thread, so large batches are priced on up to 16 threads
-  // (lc_check's multi-GPU split runs this on every call)
-  const int64_t n_rec = ops && n_keys ? key_off[n_keys] - key_off[0] : 0;
-  const int nth = (int)std::min<int64_t>(
-      16, std::max<int64_t>(1, std::min<int64_t>(n_keys, n_rec >> 18)));
-  auto price = [&](int64_t k0, int64_t k1) {
-    for (int64_t k = k0; k < k1; k++) {
-      const int64_t n = key_off[k + 1] - key_off[k];
-      pre[(size_t)k + 1] = ops ? key_cost(ops + key_off[k], n) : (double)n + 64.0;
-    }
-  };
-  for_key_ranges(n_keys, nth, price);
-  for (int64_t k = 0; k < n_keys; k++) pre[(size_t)k + 1] += pre[(size_t)k];
-  const double total = pre[(size_t)n_keys];
-  bounds[0] = 0;
-  int64_t k = 0;
-  for (int32_t p = 1; p < n_parts; p++) {
-    const double goal = total * p / n_parts;
-    while (k < n_keys && pre[(size_t)k] < goal) k++;
-    bounds[p] = k;
-  }
-  bounds[n_parts] = n_keys;
-  return 0;
-}
-
-int lc_check_ex(lc_ctx *c, const lc_op *ops, const int64_t *key_off,
-                int64_t n_keys, const lc_opts *opts, lc_key_result *out, const lc_aux *aux) {
-  if (!c) return -EINVAL;
-  return check_host(c, ops, key_off, nullptr, n_keys, opts, out, aux);
-}
-
-int lc_check(lc_ctx *c, const lc_op *ops, const int64_t *key_off,
-             int64_t n_keys, const lc_opts *opts, lc_key_result *out) {
-  return lc_check_ex(c, ops, key_off, n_keys, opts, out, nullptr);
-}
-
-int lc_check32(lc_ctx *c, const lc_op32 *ops, const int64_t *key_off, const int64_t *key_base,
-               int64_t n_keys, const lc_opts *opts, lc_key_result *out, const lc_aux *aux) {
-  if (!c) return -EINVAL;
-  if (reinterpret_cast<uintptr_t>(ops) % 4) {
-    set_err(c, "lc_check32: ops must be 4-byte aligned");
-    return -EINVAL;
-  }
-  return check_host(c, ops, key_off, key_base, n_keys, opts, out, aux);
-}
-
-int lc_check16(lc_ctx *c, const lc_op16 *ops, const int64_t *key_off, const int64_t *key_base,
-               int64_t n_keys, const lc_opts *opts, lc_key_result *out, const lc_aux *aux) {
-  if (!c) return -EINVAL;
-  if (reinterpret_cast<uintptr_t>(ops) % 4) {
-    set_err(c, "lc_check16: ops must be 4-byte aligned");
-    return -EINVAL;
-  }
-  return check_host(c, ops, key_off, key_base, n_keys, opts, out, aux);
-}
-
 int lc_last_call_profile(lc_ctx *c, lc_call_profile *out) {
   if (!c || !out) return -EINVAL;
   *out = c->prof;
@@ -2660,170 +1564,6 @@ int lc_check_device32(lc_ctx *c, const lc_op32 *d_ops, const int64_t *d_key_off,
   if (!c) return -EINVAL;
   return check_device(c, "lc_check_device32", d_ops, true, d_key_off, d_key_base, n_keys, opts, d_out,
                       stream, aux);
-}
-
-int lc_check_frontiers(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
-                       const int64_t *stop_op, const lc_opts *opts, lc_fx_config *out,
-                       int32_t max_per_key, int32_t *n_out) {
-  if (!c) return -EINVAL;
-  if (int rc = frontier_args(c, "lc_check_frontiers",
-                             n_keys < 0 || max_per_key < 1 ||
-                                 (n_keys > 0 && (!ops || !key_off || !stop_op || !out || !n_out)),
-                             key_off, n_keys))
-    return rc;
-  if (n_keys == 0) return 0;
-  lcdev::KParams p;
-  if (int rc = opts_to_params(c, opts, &p)) return rc;
-  Dev &d = c->devs[0];
-  HIP_TRY(c, hipSetDevice(d.id));
-  (void)settle_status(d);  // a fused call's status copy may still be pending
-  const size_t cfg_bytes = sizeof(lc_fx_config) * (size_t)max_per_key * (size_t)n_keys;
-  int e = ensure(c, d.d_gws, cfg_bytes);
-  if (!e) e = ensure(c, d.d_jit, sizeof(int32_t) * (size_t)n_keys);
-  if (!e) e = ensure(c, d.d_jit2, sizeof(int32_t) * (size_t)n_keys);
-  if (!e) e = frontier_upload(c, d, ops, key_off, n_keys, stop_op);
-  if (e) return e;
-  int64_t *d_off = d.d_off.p, *d_stop = d_off + (n_keys + 1);
-  int32_t *d_n = d.d_jit.p, *d_retry = d.d_jit2.p;
-  lc_fx_config *d_cfg = reinterpret_cast<lc_fx_config *>(d.d_gws.p);
-  const lc_op *d_ops = d.d_ops.p;
-  hipStream_t st = d.stream;
-  HIP_TRY(c, lcdev::launch_frontier_dump(d_ops, d_off, d_stop, n_keys, p, d_cfg, max_per_key, d_n,
-                                         d_retry, &d.d_status->n_overflow, st));
-  if ((e = read_status(c, d, st))) return e;
-  // keys whose search outgrew the LDS regions: again over HBM tables (the
-  // first HBM tier's 16k configurations per set), one wavefront per key
-  if (const int32_t n_retry = d.h_status->n_overflow) {
-    const int waves = std::min<int>(n_retry, 256);
-    if ((e = ensure(c, d.d_ws, lcdev::hbm_tier_ws_bytes(waves, kHbmCap[0])))) return e;
-    HIP_TRY(c, lcdev::launch_frontier_dump_hbm(d_ops, d_off, d_stop, d_retry, n_retry, p, d.d_ws.p, waves,
-                                               kHbmCap[0], d_cfg, max_per_key, d_n,
-                                               &d.d_status->hbm_next, st));
-  }
-  HIP_TRY(c, hipMemsetAsync(d.d_status, 0, sizeof(lcdev::KStatus), st));
-  HIP_TRY(c, hipMemcpyAsync(n_out, d_n, sizeof(int32_t) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
-  // one copy of every key's slots (C5's 94 keys x 10: 0.5 MB) rather than one
-  // per key; slots past a key's count keep the device's scratch
-  HIP_TRY(c, hipMemcpyAsync(out, d_cfg, cfg_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  d.status_dirty = false;
-  return 0;
-}
-
-int lc_check_frontiers_counted(lc_ctx *c, const lc_op *ops, const int64_t *key_off, int64_t n_keys,
-                               const int64_t *stop_op, const lc_opts *opts, lc_counted_config *out,
-                               int32_t max_per_key, int32_t *n_out, int64_t *n_total,
-                               int64_t *pending, int64_t pending_cap) {
-  if (!c) return -EINVAL;
-  if (int rc = frontier_args(c, "lc_check_frontiers_counted",
-                             n_keys < 0 || max_per_key < 1 ||
-                                 (n_keys > 0 && (!ops || !key_off || !stop_op || !out || !n_out ||
-                                                 !n_total || !pending)),
-                             key_off, n_keys))
-    return rc;
-  if (n_keys == 0) return 0;
-  if (n_keys > INT32_MAX) {  // (the device's key lists are int32)
-    set_err(c, "lc_check_frontiers_counted: more than 2^31 - 1 keys");
-    return -EINVAL;
-  }
-  const int64_t r0 = key_off[0], nrec = key_off[n_keys] - r0;
-  if (nrec > INT64_MAX / max_per_key || pending_cap < (int64_t)max_per_key * nrec) {
-    set_err(c, "lc_check_frontiers_counted: pending_cap " + std::to_string(pending_cap) +
-                   " is less than max_per_key * records");
-    return -EINVAL;
-  }
-  lcdev::KParams p;
-  if (int rc = opts_to_params(c, opts, &p)) return rc;
-  try {
-    return frontiers_counted(c, ops, key_off, n_keys, stop_op, p, out, max_per_key, n_out, n_total,
-                             pending);
-  } catch (const std::bad_alloc &) {  // (the host's tables: sized by the caller's arguments)
-    set_err(c, "lc_check_frontiers_counted: out of host memory");
-    return -ENOMEM;
-  }
-}
-
-int lc_pack32(const lc_op *ops, const int64_t *key_off, int64_t n_keys, lc_op32 *out,
-              int64_t *key_base) {
-  if (n_keys < 0 || (n_keys > 0 && (!ops || !key_off || !out || !key_base))) return -EINVAL;
-  if (n_keys == 0) return 0;
-  if (key_off[0] < 0) return -EINVAL;
-  for (int64_t k = 0; k < n_keys; k++)
-    if (key_off[k + 1] < key_off[k]) return -EINVAL;
-  constexpr int64_t kFieldMax = 0x7FFFFFFE, kNever = 0xFFFFFFFFll;
-  // the device's decoding (records.h, decode) of a 48-byte record, applied
-  // here: what it reads of each field fits 32 bits
-  auto pack = [&](int64_t k0, int64_t k1) {
-    for (int64_t k = k0; k < k1; k++) {
-      const int64_t b = key_off[k], e = key_off[k + 1];
-      const int64_t base = e > b ? ops[b].call : 0;
-      key_base[k] = base;
-      for (int64_t i = b; i < e; i++) {
-        const lc_op &o = ops[i];
-        const int64_t rc = o.call - base, rr = o.ret - base;
-        const bool bad = o.value < -1 || o.value > kFieldMax || o.expected < -1 ||
-                         o.expected > kFieldMax || o.call < 0 || o.ret <= o.call || rc < 0 ||
-                         rc >= kNever || (o.ret != LC_INF && rr >= kNever);
-        lc_op32 &q = out[i];
-        q.f = o.f >= 0 && o.f <= LC_F_CAS ? (int32_t)o.f : 3;
-        q.value = bad ? -2 : (int32_t)o.value;  // -2: malformed, in either width
-        q.expected = (int32_t)o.expected;
-        q.version = o.version < -1 || o.version > kFieldMax ? (int32_t)kFieldMax : (int32_t)o.version;
-        q.call = (uint32_t)rc;
-        // (a malformed record's return may land on LC_INF32 modulo 2^32: it
-        // stays a return, which is what the witness initialisation reads)
-        q.ret = o.ret == LC_INF ? LC_INF32 : (uint32_t)rr == LC_INF32 ? LC_INF32 - 1 : (uint32_t)rr;
-      }
-    }
-  };
-  const int64_t n_rec = key_off[n_keys] - key_off[0];
-  const int nth = (int)std::min<int64_t>(16, std::max<int64_t>(1, std::min<int64_t>(n_keys, n_rec >> 18)));
-  for_key_ranges(n_keys, nth, pack);
-  return 0;
-}
-
-int lc_pack16(const lc_op *ops, const int64_t *key_off, int64_t n_keys, lc_op16 *out,
-              int64_t *key_base) {
-  if (n_keys < 0 || (n_keys > 0 && (!ops || !key_off || !out || !key_base))) return -EINVAL;
-  if (n_keys == 0) return 0;
-  if (key_off[0] < 0) return -EINVAL;
-  for (int64_t k = 0; k < n_keys; k++)
-    if (key_off[k + 1] < key_off[k]) return -EINVAL;
-  constexpr int64_t kFieldMax = 0x7FFFFFFE, kNever = 0xFFFFFFFFll;
-  // lc_pack32's narrowing, then the ids into 15 bits (a record it marks
-  // malformed: value field 0x7FFF, its expected field clamped — the device
-  // reads nothing else of a malformed key's records)
-  std::atomic<bool> range{true};
-  auto pack = [&](int64_t k0, int64_t k1) {
-    for (int64_t k = k0; k < k1; k++) {
-      const int64_t b = key_off[k], e = key_off[k + 1];
-      const int64_t base = e > b ? ops[b].call : 0;
-      key_base[k] = base;
-      for (int64_t i = b; i < e; i++) {
-        const lc_op &o = ops[i];
-        const int64_t rc = o.call - base, rr = o.ret - base;
-        const bool bad = o.value < -1 || o.value > kFieldMax || o.expected < -1 ||
-                         o.expected > kFieldMax || o.call < 0 || o.ret <= o.call || rc < 0 ||
-                         rc >= kNever || (o.ret != LC_INF && rr >= kNever);
-        if (!bad && (o.value > LC_ID15_MAX || o.expected > LC_ID15_MAX)) {
-          range.store(false, std::memory_order_relaxed);
-          return;
-        }
-        const uint32_t f = o.f >= 0 && o.f <= LC_F_CAS ? (uint32_t)o.f : 3u;
-        const uint32_t v = bad ? 0x7FFFu : (uint32_t)(o.value + 1);
-        const uint32_t x = (uint32_t)std::min<int64_t>(0x7FFF, std::max<int64_t>(0, o.expected + 1));
-        lc_op16 &q = out[i];
-        q.fve = f << 30 | v << 15 | x;
-        q.version = o.version < -1 || o.version > kFieldMax ? (int32_t)kFieldMax : (int32_t)o.version;
-        q.call = (uint32_t)rc;
-        q.ret = o.ret == LC_INF ? LC_INF32 : (uint32_t)rr == LC_INF32 ? LC_INF32 - 1 : (uint32_t)rr;
-      }
-    }
-  };
-  const int64_t n_rec = key_off[n_keys] - key_off[0];
-  const int nth = (int)std::min<int64_t>(16, std::max<int64_t>(1, std::min<int64_t>(n_keys, n_rec >> 18)));
-  for_key_ranges(n_keys, nth, pack);
-  return range.load() ? 0 : -ERANGE;
 }
 
 }  // extern "C"

@@ -1,10 +1,13 @@
-// runtime.h — what lincheck.cpp (the register path; it defines the functions
-// declared here) shares with the side checkers' drivers (*_dev.cpp).  Internal:
-// not installed with include/, and lcrt has hidden visibility.
+// runtime.h — what lincheck.cpp (the context and the tiers; it defines the
+// functions declared here unless another file is named) shares with the rest
+// of the register path (check_host.cpp, frontiers_dev.cpp, whole_gpu.cpp) and
+// the side checkers' drivers (*_dev.cpp).  Internal: not installed with
+// include/, and lcrt has hidden visibility.
 #pragma once
 #include <errno.h>
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -15,6 +18,7 @@
 #include "kernels.h"
 #include "counted.h"
 #include "events.h"
+#include "plan_host.h"
 #include "workspace.h"
 
 namespace lcrt __attribute__((visibility("hidden"))) {
@@ -163,6 +167,9 @@ void release(SfState &s);
 void release(ApState &s);
 
 void set_err(lc_ctx *c, const std::string &s);
+// key_off[0] >= 0 and key_off monotone over n_keys > 0 keys, or -EINVAL with
+// the context's error naming the call `who`.
+int check_offsets(lc_ctx *c, const char *who, const int64_t *key_off, int64_t n_keys);
 
 #define HIP_TRY(ctx, expr)                                                   \
   do {                                                                       \
@@ -189,8 +196,92 @@ int ensure(lc_ctx *c, Buf<T> &b, size_t bytes) {
   return 0;
 }
 
+constexpr int64_t kDefaultBudget = 1 << 24;   // configurations per key
+// HBM tiers: (configurations per set, concurrent keys).  Workspace per key
+// is ~128 B per configuration of capacity (3 regions + 2 hash tables).
+// Each tier's workspace is <= 4 GiB; the first has the most waves (the
+// lane-parallel expansion is latency-bound per wave).
+constexpr int kHbmTiers = 3;
+constexpr int64_t kHbmCap[kHbmTiers] = {1 << 14, 1 << 18, 1 << 21};
+constexpr int kHbmWaves[kHbmTiers] = {2048, 128, 16};
+// A call whose pageable inputs and outputs fit in kStageMax bytes copies them
+// through the device's pinned staging buffer (a memcpy on the host, then a
+// DMA from pinned memory): the runtime's pageable path costs tens of
+// microseconds per copy, which small calls (C1, C4) pay in full.  At a few
+// MB the runtime's path is the faster one again (a 4.8 MB input staged:
+// 0.07-0.15 ms slower, profiles/r05/stage_ab.txt).
+constexpr size_t kStageMax = size_t(2) << 20;
+
+// lc_check's host-to-device pipeline on one device (check_host.cpp): the
+// device's key range cut into chunks of about kChunkBytes of records
+// (plan_host.h).  run_device calls issue(i), which enqueues chunk i's record
+// copy on the copy stream and records ready[i]; the compute stream waits for
+// that event, widens 24-byte records (lc_check32), and runs the version-order
+// (or fused) pass over the chunk's keys while the copy engine moves the next
+// chunk.  (A pageable copy may block the issuing thread until it has landed;
+// issuing each chunk's copy right before its kernels keeps the overlap
+// either way.)
+struct Chunks : ChunkPlan {
+  std::function<int(int)> issue;
+  const hipEvent_t *ready = nullptr;
+  const lc_op32 *d_ops32 = nullptr;  // staging records to widen into d_ops (null: 48-byte copies)
+  const lc_op16 *d_ops16 = nullptr;  // (lc_check16) the same for 16-byte records
+  const int64_t *d_base = nullptr;   // key bases for the widening (null: 0)
+  int64_t max_len = 0;               // longest key (records)
+};
+
+// Device-side lc_aux outputs of one run_device call (null: not wanted).
+struct AuxOut {
+  int32_t *wit = nullptr;   // per record, indexed like d_ops
+  int32_t *kind = nullptr;  // per key
+  int32_t *cert = nullptr;  // per key, 4 int32 (infeasibility certificates)
+  int32_t *cset = nullptr;  // per record (HALL position sets)
+  int64_t n_records = 0;
+};
+
+// Where a run_device call's records come from, beyond d_ops / d_off
+// (default: 48-byte records in place, offsets on the device only).
+struct Source {
+  // the shard's key offsets in host memory when the caller has them
+  // (lc_check_ex): the gap tier may then be launched early
+  const int64_t *h_off = nullptr;
+  // lc_check's chunked copies, or null: the records are in place
+  const Chunks *chunks = nullptr;
+  // the first pass over lc_op32 records (lc_check32 / lc_check_device32
+  // without lc_aux outputs): ops32 and the keys' bases (null: 0), indexed
+  // like d_ops / d_off; `widen` fills the 48-byte records the later tiers
+  // read (and names them) once a key is handed over
+  const lc_op32 *ops32 = nullptr;
+  const int64_t *base32 = nullptr;
+  std::function<int(const lc_op **)> widen;
+};
+
+bool env_is_off(const char *name);
+int opts_to_params(lc_ctx *c, const lc_opts *o, lcdev::KParams *p);
+bool is_pinned(lc_ctx *c, const void *p, size_t n);
+char *stage_buf(lc_ctx *c, Dev &d);
 int64_t settle_status(Dev &d);
+void settle_timing(lc_ctx *c, Dev &d);
+int read_status(lc_ctx *c, Dev &d, hipStream_t st);
+void fill_stats(lc_stats &s, const Dev &d);
 int res_stop(lc_ctx *c, Dev &d);
+int run_device(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
+               const lcdev::KParams &p, lc_key_result *d_out, hipStream_t st, int64_t flags,
+               const AuxOut &ao = AuxOut(), const Source &src = Source());
+int run_certificates(lc_ctx *c, Dev &d, const lc_op *d_ops, const int64_t *d_off, int64_t n_keys,
+                     const lcdev::KParams &p, const lc_key_result *d_out, hipStream_t st,
+                     const AuxOut &wo);
+
+// whole_gpu.cpp — LC_FLAG_WHOLE_GPU: the keys of `todo` searched again by
+// the frontier exchange; fetch(k, records) and store(k, result) move a key
+// between the caller's memory (host or device) and the engine.
+int whole_gpu(lc_ctx *c, const std::vector<int64_t> &todo, const lc_opts *opts,
+              const std::function<int(int64_t, std::vector<lc_op> &)> &fetch,
+              const std::function<int(int64_t, const lc_key_result &)> &store);
+void unknown_keys(const lc_key_result *res, int64_t n_keys, std::vector<int64_t> &budget,
+                  std::vector<int64_t> &window);
+int whole_gpu_device(lc_ctx *c, const lc_op *d_ops, const int64_t *d_key_off, int64_t n_keys,
+                     const lc_opts *opts, lc_key_result *d_out, int32_t *d_cert, hipStream_t st);
 int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const int64_t *d_key_off,
                  const int64_t *d_key_base, int64_t n_keys, const lc_opts *opts, lc_key_result *d_out,
                  void *stream, const lc_aux *aux);

@@ -23,13 +23,22 @@ def _dev(arr):
     return torch.from_numpy(np.ascontiguousarray(arr)).to(torch.device("cuda", 0))
 
 
-def _run(ctx, d_ops, d_off, n, flags=0):
+def _call(ctx, d_ops, d_off, n, flags=0):
+    """check_device; the results stay on the device."""
     import torch
     d_out = torch.zeros(max(n, 1) * 40, dtype=torch.uint8, device=d_ops.device)
     s = torch.cuda.current_stream(d_ops.device)
     ctx.check_device(d_ops.data_ptr(), d_off.data_ptr(), n, d_out.data_ptr(), stream=s.cuda_stream,
                      opts=abi.default_opts(flags=flags))
+    return d_out
+
+
+def _results(d_out, n):
     return np.frombuffer(d_out.cpu().numpy().tobytes(), dtype=abi.RESULT_DTYPE)[:n].copy()
+
+
+def _run(ctx, d_ops, d_off, n, flags=0):
+    return _results(_call(ctx, d_ops, d_off, n, flags), n)
 
 
 def _launched(ctx, d_ops, d_off, n, monkeypatch):
@@ -138,3 +147,74 @@ def test_contexts_reopened_signal_path(monkeypatch, resident):
             got = _run(ctx, devs[k][0], devs[k][1], 300)
         for f in ("verdict", "reason", "fail_op", "fail_prefix_end"):
             assert (got[f] == want[k][f]).all(), (i, f)
+
+
+def _crashed_key(s):
+    """18 sequential versioned writes, three crashed version-less writes (two
+    classes) among them, and a last read of a value nobody wrote: the key is
+    invalid at that read, whose return the frontier calls stop at."""
+    from helpers import INF, R, W
+    ops = [[W, (i + s) % 4 + 1, -1, i + 1, 10 * i, 10 * i + 5] for i in range(18)]
+    ops += [[W, 7, -1, -1, 33, INF], [W, 7, -1, -1, 77, INF], [W, 6, -1, -1, 121, INF]]
+    ops.append([R, 5, -1, 18, 200, 205])
+    return sorted(ops, key=lambda r: r[4])
+
+
+@pytest.mark.parametrize("batch", ["tiny", "clean"])
+@pytest.mark.parametrize("counted", [False, True], ids=["frontiers", "frontiers_counted"])
+def test_frontier_call_stops_live_grid(ctx, monkeypatch, counted, batch):
+    """A frontier call between two lc_check_device calls: the grid (idle bound
+    20 ms: live when the frontier call starts, gone by itself whatever
+    happens) leaves before the frontier kernels run and d_status is zeroed, so
+    all three calls return what they return without a grid.
+
+    `clean` (300 valid version-pinned keys) is the batch that leaves a grid
+    behind, and the test says so before the frontier call: the grid served the
+    first call (only a call it serves is timed under LC_FLAG_NO_TIMING, see
+    test_resident_totals_count_every_call), no key was handed over (a handoff
+    makes first_pass stop the grid itself) and less than half the idle bound
+    has passed since the call began (its results are read back only after the
+    frontier call: the copy would wait behind the grid).  `tiny` (2,000 keys, 303 invalid, crashed
+    ops) is the golden batch of the other tests here; its calls hand keys over,
+    so after them no grid is left for the frontier call to stop."""
+    from helpers import pack_keys
+    if batch == "tiny":
+        z = np.load(os.path.join(GOLDEN, "tiny.npz"))
+        ops, off = z["ops"], z["key_off"]
+    else:
+        ops, off = abi.synth(300, 100, concurrency=8, seed=61)[:2]
+    n = len(off) - 1
+    d_ops, d_off = _dev(ops), _dev(off)
+    want = _launched(ctx, d_ops, d_off, n, monkeypatch)
+    f_ops, f_off = pack_keys([_crashed_key(0), _crashed_key(1)])
+    stops = [len(f_ops) // 2 - 1] * 2
+
+    def frontiers(c):
+        if counted:
+            cfgs, totals = c.check_frontiers_counted(f_ops, f_off, stops, 10)
+            return cfgs, [int(t) for t in totals]
+        return c.check_frontiers(f_ops, f_off, stops, 10)
+
+    with abi.Context(device_mask=1) as fresh:  # (never starts a grid)
+        want_f = frontiers(fresh)
+    cfgs = want_f[0] if counted else want_f
+    assert all(c is not None and len(c) == 1 and len(c[0][2]) == 4 for c in cfgs), cfgs
+    monkeypatch.setenv("LC_RESIDENT_IDLE_US", "20000")
+    for attempt in range(5):  # (again if the host was held up between the two calls)
+        ctx.totals(reset=True)
+        t0 = time.perf_counter()
+        d_first = _call(ctx, d_ops, d_off, n, abi.LC_FLAG_NO_TIMING)
+        st = ctx.stats()
+        served = ctx.totals(reset=True)["timed_calls"] == 1
+        kept = st["n_gap_keys"] == 0 and st["n_jit_keys"] == 0 and st["gap_kernel_ms"] == 0
+        live = time.perf_counter() - t0 < 0.010
+        if batch == "tiny" or (served and kept and live):
+            break
+    if batch == "clean":
+        assert served and kept and live, (served, kept, time.perf_counter() - t0)
+    got_f = frontiers(ctx)
+    first = _results(d_first, n)
+    second = _run(ctx, d_ops, d_off, n)
+    assert got_f == want_f
+    for f in FIELDS:
+        assert (first[f] == want[f]).all() and (second[f] == want[f]).all(), f

@@ -1,4 +1,4 @@
-// Host cost of lc_check's device split (lincheck.cpp plan_devices) on a
+// Host cost of lc_check's device split (csrc/plan_host.h plan_devices) on a
 // C2-sized batch: the sampled irregularity scan at several strides and
 // thread counts, and the cost of creating the threads alone.
 //   g++ -O2 -std=c++17 -pthread tools/plan_probe.cpp -o /tmp/plan_probe && /tmp/plan_probe
