@@ -575,5 +575,7 @@ const char *lc_build_id(void);
 #include "lincheck_setfull.h"
 /* lc_append_check: Elle's list-append checker with the graph on the device */
 #include "lincheck_append.h"
+/* lc_wr_check: Elle's rw-register checker (the :wr workload) on the device */
+#include "lincheck_wr.h"
 
 #endif /* LINCHECK_H */

@@ -243,6 +243,46 @@ class LcApLimits(ctypes.Structure):
                 ("max_position", ctypes.c_int64), ("max_mops", ctypes.c_int64)]
 
 
+# lc_wr_check (include/lincheck_wr.h): the txn, edge and step records are
+# list-append's
+LC_WR_OK, LC_WR_INFO, LC_WR_FAIL = 0, 1, 2
+LC_WR_WRITE, LC_WR_READ = 0, 1
+LC_WR_NIL = -2 ** 63
+LC_WR_WFR_KEYS = 1
+LC_WR_R_INTERNAL, LC_WR_R_PHANTOM, LC_WR_R_G1A, LC_WR_R_G1B, LC_WR_R_EXTERNAL = 1, 2, 4, 8, 16
+LC_WR_R_ANOMALY = 15
+LC_WR_K_CYCLIC, LC_WR_K_LOST_UPDATE = 1, 2
+WR_TXN_DTYPE, WR_EDGE_DTYPE, WR_STEP_DTYPE = AP_TXN_DTYPE, AP_EDGE_DTYPE, AP_STEP_DTYPE
+WR_MOP_DTYPE = np.dtype([("key", "<i8"), ("value", "<i8"), ("f", "<i4"), ("known", "<i4")])
+WR_KEY_DTYPE = np.dtype([("key", "<i8"), ("cyc_value", "<i8"), ("flags", "<i4"), ("n_writes", "<i4"),
+                         ("n_versions", "<i4"), ("n_ext_reads", "<i4")])
+assert (WR_MOP_DTYPE.itemsize, WR_KEY_DTYPE.itemsize) == (24, 32)
+
+
+class LcWrOut(ctypes.Structure):
+    _fields_ = [("mop_flags", ctypes.c_void_p), ("txn_flags", ctypes.c_void_p), ("keys", ctypes.c_void_p),
+                ("edges", ctypes.c_void_p), ("edge_cap", ctypes.c_int64)] + \
+               [(f, ctypes.c_void_p) for f in ("byc", "rt_lo", "rt_hi", "scc", "scc_class", "steps", "cycle_off",
+                                               "cycle_scc")]
+
+
+class LcWrSummary(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("n_internal", ctypes.c_int64), ("n_phantom", ctypes.c_int64), ("n_g1a", ctypes.c_int64),
+                ("n_g1b", ctypes.c_int64), ("n_cyclic_keys", ctypes.c_int64), ("n_lost_update", ctypes.c_int64),
+                ("n_class", ctypes.c_int64 * 8),
+                ("n_keys", ctypes.c_int64), ("n_versions", ctypes.c_int64), ("n_ok", ctypes.c_int64),
+                ("n_nodes", ctypes.c_int64), ("n_edges", ctypes.c_int64), ("n_edges_raw", ctypes.c_int64),
+                ("n_scc", ctypes.c_int64), ("n_cycles_returned", ctypes.c_int64),
+                ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("host_graph_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
+class LcWrLimits(ctypes.Structure):
+    _fields_ = [("max_edges", ctypes.c_int64), ("default_max_edges", ctypes.c_int64),
+                ("max_position", ctypes.c_int64), ("max_mops", ctypes.c_int64)]
+
+
 class LcSynthParams(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("ops_per_key", ctypes.c_int64),
                 ("concurrency", ctypes.c_int32), ("n_values", ctypes.c_int32),
@@ -381,6 +421,14 @@ def lib():
             L.lc_append_check.restype = ctypes.c_int
             L.lc_append_limits.argtypes = [ctypes.POINTER(LcApLimits)]
             L.lc_append_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_wr_check"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            wr = [p, i64, p, i64, ctypes.c_uint32, ctypes.POINTER(LcWrOut), ctypes.POINTER(LcWrSummary)]
+            L.lc_wr_check_host.argtypes = wr
+            L.lc_wr_check_host.restype = ctypes.c_int
+            L.lc_wr_check.argtypes = [vp] + wr
+            L.lc_wr_check.restype = ctypes.c_int
+            L.lc_wr_limits.argtypes = [ctypes.POINTER(LcWrLimits)]
+            L.lc_wr_limits.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -608,6 +656,78 @@ def append_limits():
     return {f: getattr(s, f) for f, _ in LcApLimits._fields_}
 
 
+class _WrCall:
+    """One lc_wr_check(_host) call's arrays: the inputs made contiguous, the
+    outputs allocated as the header sizes them, the edges with room for
+    edge_cap (None: two per mop and 16, which a history without large reader
+    x writer products stays within)."""
+
+    def __init__(self, txns, mops, wfr_keys=True, edge_cap=None):
+        self.txns = np.ascontiguousarray(txns, dtype=WR_TXN_DTYPE)
+        self.mops = np.ascontiguousarray(mops, dtype=WR_MOP_DTYPE)
+        self.flags = LC_WR_WFR_KEYS if wfr_keys else 0
+        nt, nm = max(len(self.txns), 1), max(len(self.mops), 1)
+        self.edge_cap = 2 * len(self.mops) + 16 if edge_cap is None else int(edge_cap)
+        i4 = lambda n: np.zeros(n, dtype=np.int32)  # noqa: E731
+        self.arrays = {
+            "mop_flags": i4(nm), "txn_flags": i4(nt), "keys": np.zeros(nm, dtype=WR_KEY_DTYPE),
+            "edges": np.zeros(max(self.edge_cap, 1), dtype=WR_EDGE_DTYPE),
+            "byc": i4(nt), "rt_lo": i4(nt), "rt_hi": i4(nt), "scc": i4(nt), "scc_class": i4(nt),
+            "steps": np.zeros(nt, dtype=WR_STEP_DTYPE),
+            "cycle_off": np.zeros(LC_AP_MAX_CYCLES + 1, dtype=np.int64), "cycle_scc": i4(LC_AP_MAX_CYCLES),
+        }
+        self.out = LcWrOut(edge_cap=self.edge_cap, **{k: _ptr(v) for k, v in self.arrays.items()})
+        self.summary = LcWrSummary()
+
+    def args(self):
+        return (_ptr(self.txns), len(self.txns), _ptr(self.mops), len(self.mops), self.flags,
+                ctypes.byref(self.out), ctypes.byref(self.summary))
+
+    def result(self):
+        """-> (a dict of the output arrays cut to their counts, the summary as a dict)."""
+        s = {}
+        for f, _ in LcWrSummary._fields_:
+            v = getattr(self.summary, f)
+            s[f] = list(v) if f == "n_class" else v
+        a, nt, nm = self.arrays, len(self.txns), len(self.mops)
+        n_steps = int(a["cycle_off"][s["n_cycles_returned"]])
+        out = {"mop_flags": a["mop_flags"][:nm], "txn_flags": a["txn_flags"][:nt], "keys": a["keys"][:s["n_keys"]],
+               "edges": a["edges"][:s["n_edges"]], "byc": a["byc"][:s["n_ok"]], "rt_lo": a["rt_lo"][:nt],
+               "rt_hi": a["rt_hi"][:nt], "scc": a["scc"][:nt], "scc_class": a["scc_class"][:nt],
+               "steps": a["steps"][:n_steps], "cycle_off": a["cycle_off"][:s["n_cycles_returned"] + 1],
+               "cycle_scc": a["cycle_scc"][:s["n_cycles_returned"]]}
+        return out, s
+
+
+def _wr_run(fn, who, error_text, txns, mops, wfr_keys, edge_cap):
+    """The call, made again with room where the edges did not fit a default
+    edge_cap (-ENOSPC leaves n_edges in the summary for that)."""
+    call = _WrCall(txns, mops, wfr_keys, edge_cap)
+    rc = fn(call)
+    if rc == -28 and edge_cap is None:
+        call = _WrCall(call.txns, call.mops, wfr_keys, int(call.summary.n_edges))
+        rc = fn(call)
+    if rc != 0:
+        raise LcError(rc, error_text() if rc in (-22, -7, -28) else who)
+    return call.result()
+
+
+def wr_check_host(txns, mops, wfr_keys=True, edge_cap=None):
+    """lc_wr_check_host: rw-register's rules on the host -> (a dict of the
+    output arrays of include/lincheck_wr.h's lc_wr_out, the summary as a dict)."""
+    return _wr_run(lambda call: lib().lc_wr_check_host(*call.args()), "lc_wr_check_host",
+                   lambda: "lc_wr_check_host", txns, mops, wfr_keys, edge_cap)
+
+
+def wr_limits():
+    """lc_wr_limits: {"max_edges", "default_max_edges", "max_position", "max_mops"}."""
+    s = LcWrLimits()
+    rc = lib().lc_wr_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_wr_limits")
+    return {f: getattr(s, f) for f, _ in LcWrLimits._fields_}
+
+
 class Context:
     """An lc_ctx on the GPUs of device_mask (0 = all)."""
 
@@ -800,6 +920,11 @@ class Context:
         if rc != 0:
             raise LcError(rc, self.last_error() if rc in (-22, -7) else "lc_append_check")
         return call.result()
+
+    def wr_check(self, txns, mops, wfr_keys=True, edge_cap=None):
+        """lc_wr_check: wr_check_host's result, with rules 1-8 on the device."""
+        return _wr_run(lambda call: lib().lc_wr_check(self._h, *call.args()), "lc_wr_check", self.last_error,
+                       txns, mops, wfr_keys, edge_cap)
 
     def set_full(self, adds, reads, read_values, linearizable=True):
         """lc_set_full: set_full_host's result, computed on the device."""

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../../include/lincheck_append.h"
+#include "graph_host.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -95,10 +96,10 @@ int64_t rules34_direct(const lc_ap_txn *txns, const lc_ap_mop *mops, const int64
 // first_dup of one key's order from its definition (phantoms included).
 int32_t first_dup_direct(const int64_t *order, int32_t len);
 
-// Rule 6 on the host.
-void real_time_host(const lc_ap_txn *txns, int64_t n_txns, int32_t *byc, int32_t *rt_lo, int32_t *rt_hi);
+// Rule 6 on the host (graph_host.cpp).
+using lcgraph::real_time_host;
 
-// Rule 7 and rule 8 over finished flags, keys, edges and ranges: out->scc,
+// Rule 7 (graph_host.cpp's cycles_host) and rule 8 over finished flags, keys, edges and ranges: out->scc,
 // scc_class, steps, cycle_off, cycle_scc, and every field of sum but the
 // read counts (taken from counts[kCounters]), n_slow_reads and the device times.
 void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,

@@ -162,9 +162,17 @@ struct ApState {  // lc_append_check
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
 };
 
+struct WrState {  // lc_wr_check
+  Buf<char> arena;
+  int64_t *h_small = nullptr;  // pinned: the status words, the four counts, the rw items' count, the counters
+  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
+};
+
 void release(EvState &s);
 void release(SfState &s);
 void release(ApState &s);
+void release(WrState &s);
 
 void set_err(lc_ctx *c, const std::string &s);
 // key_off[0] >= 0 and key_off monotone over n_keys > 0 keys, or -EINVAL with
@@ -323,4 +331,5 @@ struct lc_ctx {
   lcrt::EvState evs;       // lc_check_events
   lcrt::SfState sfs;       // lc_set_full
   lcrt::ApState aps;       // lc_append_check
+  lcrt::WrState wrs;       // lc_wr_check
 };

@@ -2,7 +2,8 @@
 // AddressSanitizer and UBSan, as a stand-alone program (host code only; no
 // GPU, no python).  From the repository's root:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-omit-frame-pointer \
-//       tools/append_host_sanitize.cpp jepsen/etcd_amd/csrc/append_host.cpp -o /tmp/append_host_sanitize
+//       tools/append_host_sanitize.cpp jepsen/etcd_amd/csrc/append_host.cpp \
+//       jepsen/etcd_amd/csrc/graph_host.cpp -o /tmp/append_host_sanitize
 //   /tmp/append_host_sanitize
 // It runs a few of tests/golden/append_kat.json's histories, written out
 // below as arrays, a refused input, and an SCC with every edge type; prints
