@@ -42,6 +42,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "cert_layout.h"
 #include "kernels.h"
 #include "records.h"
 #include "wave.h"
@@ -369,7 +370,9 @@ __global__ __launch_bounds__(kCertThreads) void cert_kernel(
     return;
   }
   // two open positions whose only candidates disagree on the value between
-  // them (or a required holder before an open one)
+  // them.  (The held_rec[q - 1] alternative is unreachable: the scan above
+  // drops a CAS that expects another value than a required holder of q-1
+  // left, so such a q is empty and has returned as HALL.  Kept as a guard.)
   for (int q = 1 + tid; q < M; q += kCertThreads) {
     if (cnt[q] != 1 || kops[held_cnt[q]].f != LC_F_CAS) continue;
     const int a = held_rec[q - 1] != INT_MAX ? held_rec[q - 1] : cnt[q - 1] == 1 ? held_cnt[q - 1] : -1;
@@ -408,9 +411,19 @@ __global__ __launch_bounds__(kCertThreads) void cert_kernel(
   // holder per position (held_cnt), the assumed ops (mark), the log of
   // assumed positions and the case-split frames (lo64's slots)
   int *glist = cnt, *asg = held_cnt, *used = mark;
+  // (cert_layout.h: both inside this key's 2 (n + 2) ints for every n; the
+  // frames are int32 fields, the region being 8-byte aligned only)
   int *logp = reinterpret_cast<int *>(lo64);
-  int4 *frames = reinterpret_cast<int4 *>(logp + ((n + 2 + 3) & ~3));
-  const int n_frames = (n + 2) / 4;
+  int *frames = logp + cert_logp_ints(n);
+  const int n_frames = cert_n_frames(n);
+  auto frame_get = [&](int i) {
+    const int *f = frames + kCertFrameInts * i;
+    return make_int4(f[0], f[1], f[2], f[3]);
+  };
+  auto frame_set = [&](int i, int4 v) {  // (lane 0 only)
+    int *f = frames + kCertFrameInts * i;
+    f[0] = v.x, f[1] = v.y, f[2] = v.z, f[3] = v.w;
+  };
   int ng = 0;  // the open positions, in order
   for (int g = 0; g < M; g++)
     if (held_rec[g] == INT_MAX) {
@@ -516,7 +529,7 @@ __global__ __launch_bounds__(kCertThreads) void cert_kernel(
       // the innermost split with a case left
       bool resumed = false;
       while (sp > 0) {
-        const int4 fr = frames[sp - 1];
+        const int4 fr = frame_get(sp - 1);
         // undo the assumptions made inside the case, then the case's own
         while (nlog > fr.z) {
           nlog--;
@@ -534,7 +547,7 @@ __global__ __launch_bounds__(kCertThreads) void cert_kernel(
           if (tid == 0) cands(fr.x, fr.w, &x);
           x = uni(x);
           if (x == INT_MAX) break;  // (cannot happen: the split counted its cases)
-          if (tid == 0) frames[sp - 1] = make_int4(fr.x, (k << 16) | (i + 1), fr.z, x);
+          if (tid == 0) frame_set(sp - 1, make_int4(fr.x, (k << 16) | (i + 1), fr.z, x));
           assign(fr.x, x, nlog);
           sync();
           resumed = true;
@@ -564,7 +577,7 @@ __global__ __launch_bounds__(kCertThreads) void cert_kernel(
     x = uni(x);
     if (tid == 0) {
       ks[T] = token(2, b, bk);
-      frames[sp] = make_int4(b, bk << 16, nlog, x);
+      frame_set(sp, make_int4(b, bk << 16, nlog, x));
     }
     T++;
     sp++;

@@ -22,6 +22,7 @@ from helpers import INF, pack_keys
 from jepsen.etcd_amd import abi
 from test_gpu_single_pass import both_paths
 from test_gpu_witness import certify
+from test_planted_cert import existing_certs
 from test_resident import FIELDS, _dev, _launched, _run
 
 pytestmark = pytest.mark.gpu
@@ -66,6 +67,36 @@ def test_check_two_pass_and_fused(ctx, monkeypatch, name):
     # version-pinned keys: a linearization of every valid key, of the prefix
     # before the failing return of every invalid one
     assert (kind == np.where(r["verdict"] == 1, abi.LC_WITNESS_FULL, abi.LC_WITNESS_PREFIX)).all()
+
+
+@pytest.mark.parametrize("path", ["check-0", "check-1", "check32-0", "check32-1", "check16"])
+@pytest.mark.parametrize("name", GROUPS)
+def test_certificates_equal_the_restatement(ctx, monkeypatch, name, path):
+    """Certificates asked for on the same batches, through lc_check,
+    lc_check32 (LC_FUSED=0 and 1 each) and lc_check16: every invalid plant's
+    (kind, a, b, c) is the one tests/cert_ref.py finds at the plant's failing
+    return (none of these kinds carries a set), oracle/cert.c accepts it, and
+    every valid key carries LC_CERT_NONE."""
+    pls, ops, off, _ = batch(name)
+    inv, certs = existing_certs(name)
+    want = {pl.tag: c for pl, (_, c) in zip(inv, sorted(certs.items()))}
+    fn, _, fused = path.partition("-")
+    if fused:
+        monkeypatch.setenv("LC_FUSED", fused)
+    if fn == "check":
+        _, r, _, _, cert, cset = ctx.check(ops, off, witness=True, certificate=True)
+    elif fn == "check32":
+        o32, base = abi.pack32(ops, off)
+        _, r, _, _, cert, cset = ctx.check32(o32, off, base, certificate=True)
+    else:
+        o16, base = abi.pack16(ops, off)
+        _, r, _, _, cert, cset = ctx.check16(o16, off, base, certificate=True)
+    same_as_oracle(name, r)
+    for k, pl in enumerate(pls):
+        w = want[pl.tag] if pl.verdict == 0 else (abi.LC_CERT_NONE, -1, -1, 0, [])
+        assert tuple(int(x) for x in cert[k]) == tuple(w[:4]) and not w[4], (pl.tag, cert[k], w)
+    st = oracle.check_certificate(ops, off, cert.reshape(-1), cset, r, n_threads=16)
+    assert (st == np.where(r["verdict"] == 0, oracle.CERT_OK, oracle.CERT_NONE)).all()
 
 
 @pytest.mark.parametrize("fused", ["0", "1"])
