@@ -577,5 +577,7 @@ const char *lc_build_id(void);
 #include "lincheck_append.h"
 /* lc_wr_check: Elle's rw-register checker (the :wr workload) on the device */
 #include "lincheck_wr.h"
+/* lc_watch_check: the :watch workload's log-convergence checker on the device */
+#include "lincheck_watch.h"
 
 #endif /* LINCHECK_H */

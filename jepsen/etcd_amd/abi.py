@@ -283,6 +283,36 @@ class LcWrLimits(ctypes.Structure):
                 ("max_position", ctypes.c_int64), ("max_mops", ctypes.c_int64)]
 
 
+# lc_watch_check (include/lincheck_watch.h)
+LC_WT_DELETE, LC_WT_INSERT = 0, 1
+LC_WT_NO_SCRIPT = 1
+LC_WT_MAX_D_LIMIT = 4096
+WT_THREAD_DTYPE = np.dtype([("off", "<i8"), ("len", "<i8"), ("revision", "<i8"), ("thread", "<i8")])
+WT_DELTA_DTYPE = np.dtype([("thread", "<i4"), ("flags", "<u4"), ("edit_distance", "<i8"), ("prefix", "<i8"),
+                           ("suffix", "<i8"), ("script_off", "<i8"), ("script_len", "<i8")])
+WT_EDIT_DTYPE = np.dtype([("at", "<i8"), ("value", "<i8"), ("op", "<i4"), ("pad", "<i4")])
+assert (WT_THREAD_DTYPE.itemsize, WT_DELTA_DTYPE.itemsize, WT_EDIT_DTYPE.itemsize) == (32, 48, 24)
+
+
+class LcWtOut(ctypes.Structure):
+    _fields_ = [("cls", ctypes.c_void_p), ("distance", ctypes.c_void_p), ("deltas", ctypes.c_void_p),
+                ("edits", ctypes.c_void_p), ("edit_cap", ctypes.c_int64)]
+
+
+class LcWtSummary(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int32), ("canonical", ctypes.c_int32), ("canonical_size", ctypes.c_int64),
+                ("n_threads", ctypes.c_int64), ("n_classes", ctypes.c_int64), ("n_deltas", ctypes.c_int64),
+                ("n_edits", ctypes.c_int64), ("n_no_script", ctypes.c_int64), ("n_by_host", ctypes.c_int64),
+                ("n_collisions", ctypes.c_int64), ("revisions_equal", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
+class LcWtLimits(ctypes.Structure):
+    _fields_ = [("max_d", ctypes.c_int64), ("default_max_d", ctypes.c_int64), ("trace_bytes", ctypes.c_int64),
+                ("default_trace_bytes", ctypes.c_int64), ("max_len", ctypes.c_int64),
+                ("max_device_len", ctypes.c_int64), ("hash_mask", ctypes.c_uint64)]
+
+
 class LcSynthParams(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("ops_per_key", ctypes.c_int64),
                 ("concurrency", ctypes.c_int32), ("n_values", ctypes.c_int32),
@@ -429,6 +459,14 @@ def lib():
             L.lc_wr_check.restype = ctypes.c_int
             L.lc_wr_limits.argtypes = [ctypes.POINTER(LcWrLimits)]
             L.lc_wr_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_watch_check"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            wt = [p, i64, p, i64, i64, ctypes.c_uint32, ctypes.POINTER(LcWtOut), ctypes.POINTER(LcWtSummary)]
+            L.lc_watch_check_host.argtypes = wt
+            L.lc_watch_check_host.restype = ctypes.c_int
+            L.lc_watch_check.argtypes = [vp] + wt
+            L.lc_watch_check.restype = ctypes.c_int
+            L.lc_watch_limits.argtypes = [ctypes.POINTER(LcWtLimits)]
+            L.lc_watch_limits.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -728,6 +766,68 @@ def wr_limits():
     return {f: getattr(s, f) for f, _ in LcWrLimits._fields_}
 
 
+class _WatchCall:
+    """One lc_watch_check(_host) call's arrays: the inputs made contiguous,
+    the outputs allocated as the header sizes them, the edits with room for
+    edit_cap (None: 4,096, and as many as the call then asks for)."""
+
+    def __init__(self, threads, values, n_nonmonotonic=0, flags=0, edit_cap=None):
+        self.threads = np.ascontiguousarray(threads, dtype=WT_THREAD_DTYPE)
+        self.values = np.ascontiguousarray(values, dtype=np.int64)
+        self.n_nonmonotonic, self.flags = int(n_nonmonotonic), int(flags)
+        nt = max(len(self.threads), 1)
+        self.edit_cap = 4096 if edit_cap is None else int(edit_cap)
+        self.arrays = {"cls": np.zeros(nt, dtype=np.int32), "distance": np.zeros(nt, dtype=np.int64),
+                       "deltas": np.zeros(nt, dtype=WT_DELTA_DTYPE),
+                       "edits": np.zeros(max(self.edit_cap, 1), dtype=WT_EDIT_DTYPE)}
+        self.out = LcWtOut(edit_cap=self.edit_cap, **{k: _ptr(v) for k, v in self.arrays.items()})
+        self.summary = LcWtSummary()
+
+    def args(self):
+        return (_ptr(self.threads), len(self.threads), _ptr(self.values), len(self.values), self.n_nonmonotonic,
+                self.flags, ctypes.byref(self.out), ctypes.byref(self.summary))
+
+    def result(self):
+        """-> (a dict of the output arrays cut to their counts, the summary as a dict)."""
+        s = {f: getattr(self.summary, f) for f, _ in LcWtSummary._fields_}
+        a, nt = self.arrays, len(self.threads)
+        return {"cls": a["cls"][:nt], "distance": a["distance"][:nt], "deltas": a["deltas"][:s["n_deltas"]],
+                "edits": a["edits"][:s["n_edits"]]}, s
+
+
+def _watch_run(fn, who, error_text, threads, values, n_nonmonotonic, flags, edit_cap):
+    """The call, made again with room where the scripts did not fit a default
+    edit_cap (-ENOSPC leaves n_edits in the summary for that)."""
+    call = _WatchCall(threads, values, n_nonmonotonic, flags, edit_cap)
+    rc = fn(call)
+    if rc == -28 and edit_cap is None:
+        call = _WatchCall(call.threads, call.values, n_nonmonotonic, flags, int(call.summary.n_edits))
+        rc = fn(call)
+    if rc != 0:
+        err = LcError(rc, error_text() if rc in (-22, -7, -28) else who)
+        err.n_edits = int(call.summary.n_edits) if rc == -28 else None
+        raise err
+    return call.result()
+
+
+def watch_check_host(threads, values, n_nonmonotonic=0, flags=0, edit_cap=None):
+    """lc_watch_check_host: the watch checker's rules on the host -> (a dict of
+    the output arrays of include/lincheck_watch.h's lc_wt_out, the summary as a
+    dict).  -ENOSPC with a given edit_cap raises LcError with n_edits set."""
+    return _watch_run(lambda call: lib().lc_watch_check_host(*call.args()), "lc_watch_check_host",
+                      lambda: "lc_watch_check_host", threads, values, n_nonmonotonic, flags, edit_cap)
+
+
+def watch_limits():
+    """lc_watch_limits: {"max_d", "default_max_d", "trace_bytes", "default_trace_bytes", "max_len",
+    "max_device_len", "hash_mask"}."""
+    s = LcWtLimits()
+    rc = lib().lc_watch_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_watch_limits")
+    return {f: getattr(s, f) for f, _ in LcWtLimits._fields_}
+
+
 class Context:
     """An lc_ctx on the GPUs of device_mask (0 = all)."""
 
@@ -920,6 +1020,12 @@ class Context:
         if rc != 0:
             raise LcError(rc, self.last_error() if rc in (-22, -7) else "lc_append_check")
         return call.result()
+
+    def watch_check(self, threads, values, n_nonmonotonic=0, flags=0, edit_cap=None):
+        """lc_watch_check: watch_check_host's result, with the hashes, the
+        compares, the forward passes and the backtracks on the device."""
+        return _watch_run(lambda call: lib().lc_watch_check(self._h, *call.args()), "lc_watch_check",
+                          self.last_error, threads, values, n_nonmonotonic, flags, edit_cap)
 
     def wr_check(self, txns, mops, wfr_keys=True, edge_cap=None):
         """lc_wr_check: wr_check_host's result, with rules 1-8 on the device."""

@@ -169,10 +169,17 @@ struct WrState {  // lc_wr_check
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
 };
 
+struct WtState {  // lc_watch_check
+  Buf<char> arena;
+  // e0 .. e1: the inputs' copies; k0 .. k1: around each run of kernels in turn
+  hipEvent_t e0 = nullptr, e1 = nullptr, k0 = nullptr, k1 = nullptr;
+};
+
 void release(EvState &s);
 void release(SfState &s);
 void release(ApState &s);
 void release(WrState &s);
+void release(WtState &s);
 
 void set_err(lc_ctx *c, const std::string &s);
 // key_off[0] >= 0 and key_off monotone over n_keys > 0 keys, or -EINVAL with
@@ -332,4 +339,5 @@ struct lc_ctx {
   lcrt::SfState sfs;       // lc_set_full
   lcrt::ApState aps;       // lc_append_check
   lcrt::WrState wrs;       // lc_wr_check
+  lcrt::WtState wts;       // lc_watch_check
 };
