@@ -42,6 +42,7 @@
 #include "counted.h"
 #include "records.h"
 #include "wave.h"
+#include "rec_xpose.h"
 #include "gapmatch.h"
 
 namespace lcdev {
@@ -1912,6 +1913,39 @@ __device__ __forceinline__ void fast_issue(const lc_op *__restrict__ kops, int n
   }
 }
 
+// fast_tier_kernel's records (rec_xpose.h).  Lane i loading record i touches
+// every 128-byte line with three instructions; here wave w reads the 3 KB of
+// its 64 records of group u (records 256 u + 64 w ... + 63) as three
+// coalesced 1-KB non-temporal wave-instructions, lane l taking 16-byte chunk
+// 64 i + l of them with instruction i.  Until rec_land the 48 bytes of w[u]
+// are those three chunks, not a record; pass 1 lands each group where it
+// first touches it (the later groups' loads still in flight), and pass 2
+// reads the landed records.  Chunks at or past 3 n read as zeros, so records
+// >= n are the zeros fast_issue above gives them.
+struct FastRecsX {
+  mutable Raw w[kPer];
+};
+__device__ __forceinline__ void fast_issue(const lc_op *__restrict__ kops, int n, int tid,
+                                           FastRecsX &b) {
+  const XpKey k = xp_key(kops, n * (int)sizeof(lc_op));
+  const int lane = tid & (kWave - 1), w = tid / kWave;
+#pragma unroll
+  for (int u = 0; u < kPer; u++) {
+    const xp_u32x4 x = xp_load<true>(k, xp_chunk(u, w, 0, lane, kFastThreads));
+    const xp_u32x4 y = xp_load<true>(k, xp_chunk(u, w, 1, lane, kFastThreads));
+    const xp_u32x4 z = xp_load<true>(k, xp_chunk(u, w, 2, lane, kFastThreads));
+    __builtin_memcpy(&b.w[u].a, &x, 16);
+    __builtin_memcpy(&b.w[u].b, &y, 16);
+    __builtin_memcpy(&b.w[u].c, &z, 16);
+  }
+}
+// Called by pass 1 once per record group, with every lane of the wave
+// active, before the group's first rec_raw.
+__device__ __forceinline__ void rec_land(const FastRecs &, int, int) {}
+__device__ __forceinline__ void rec_land(const FastRecsX &b, int u, int lane) {
+  wave_xpose48(b.w[u], lane);
+}
+
 // The same records as lc_op32 (ABI 4): one thread's 24-byte records as
 // loaded — (f, value), (expected, version), (call, ret) — widened to the
 // 48-byte form only as pass 1 reads each (rec_raw), so the registers in
@@ -1941,7 +1975,9 @@ __device__ __forceinline__ void fast_issue(const lc_op32 *__restrict__ kops, int
   }
 }
 
+__device__ __forceinline__ void rec_land(const FastRecs32 &, int, int) {}
 __device__ __forceinline__ const Raw &rec_raw(const FastRecs &b, int u, int64_t) { return b.w[u]; }
+__device__ __forceinline__ const Raw &rec_raw(const FastRecsX &b, int u, int64_t) { return b.w[u]; }
 __device__ __forceinline__ Raw rec_raw(const FastRecs32 &b, int u, int64_t kbase) {
   const Raw32 &q = b.w[u];
   Raw r;
@@ -2562,6 +2598,7 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
 #pragma unroll
   for (int u = 0; u < kPer; u++) {
     const int r = tid + u * kFastThreads;
+    rec_land(b, u, lane);  // (outside r < n: all lanes)
     auto &&bw = rec_raw(b, u, kbase);
 
     bool placed = false;
@@ -2788,7 +2825,7 @@ __device__ __forceinline__ void fast_key(int64_t key, int64_t n64, const Op *__r
   }
 }
 
-template <int MODE>
+template <int MODE, class Recs = FastRecs>
 __device__ __forceinline__ void fast_one(const lc_op *__restrict__ ops,
                                          const int64_t *__restrict__ key_off, int64_t key,
                                          const KParams &p, FastLds &s,
@@ -2803,7 +2840,7 @@ __device__ __forceinline__ void fast_one(const lc_op *__restrict__ ops,
   if (MODE == kModeFast && threadIdx.x == 0)
     atomicAdd(&g_fp[0], (unsigned long long)(__builtin_amdgcn_s_memtime() - fp_e));  // offsets
 #endif
-  FastRecs r;
+  Recs r;
   if (end - beg > 0 && end - beg <= kFastMax) fast_issue(kops, (int)(end - beg), threadIdx.x, r);
   if (threadIdx.x == 0) s.raised = 0;
   fast_key<MODE>(key, end - beg, kops, 0, r, p, s, out, o,
@@ -2839,7 +2876,7 @@ __global__ __launch_bounds__(kFastThreads) void fast_tier_kernel(
     int32_t *__restrict__ h_handoff) {
   __shared__ FastLds s;
   const FastSinks o{flags, status, h_handoff, nullptr, nullptr, nullptr};
-  fast_one<kModeFast>(ops, key_off, blockIdx.x, p, s, out, o);
+  fast_one<kModeFast, FastRecsX>(ops, key_off, blockIdx.x, p, s, out, o);
 #ifdef LC_FAST_PROF
   if (threadIdx.x == 0 && atomicAdd(&g_fpdone, 1u) == gridDim.x - 1) {
     printf("fastprof keys %u offsets %llu land+init %llu pass1 %llu order+pass2 %llu timing %llu result %llu\n",
