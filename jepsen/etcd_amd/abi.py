@@ -634,35 +634,28 @@ def set_full_limits():
     return {f: getattr(s, f) for f, _ in LcSfLimits._fields_}
 
 
-class _AppendCall:
-    """One lc_append_check(_host) call's arrays: the inputs made contiguous,
-    the outputs allocated as the header sizes them."""
+class _TxnGraphCall:
+    """What one lc_append_check / lc_wr_check call (device or host) has beside
+    its inputs: the output arrays both lc_ap_out and lc_wr_out name, allocated
+    as the headers size them, and the summary."""
 
-    def __init__(self, txns, mops, values):
-        self.txns = np.ascontiguousarray(txns, dtype=AP_TXN_DTYPE)
-        self.mops = np.ascontiguousarray(mops, dtype=AP_MOP_DTYPE)
-        self.values = np.ascontiguousarray(values, dtype=np.int64)
+    def _outputs(self, key_dtype, edge_room):
+        """-> the arrays' pointers by name, for the call's out struct."""
         nt, nm = max(len(self.txns), 1), max(len(self.mops), 1)
-        n_reads = int((self.mops["f"] == LC_AP_READ).sum())
         i4 = lambda n: np.zeros(n, dtype=np.int32)  # noqa: E731
         self.arrays = {
-            "mop_flags": i4(nm), "txn_flags": i4(nt), "keys": np.zeros(nm, dtype=AP_KEY_DTYPE),
-            "edges": np.zeros(max(n_reads + len(self.mops), 1), dtype=AP_EDGE_DTYPE),  # 2 reads + appends
+            "mop_flags": i4(nm), "txn_flags": i4(nt), "keys": np.zeros(nm, dtype=key_dtype),
+            "edges": np.zeros(max(edge_room, 1), dtype=AP_EDGE_DTYPE),
             "byc": i4(nt), "rt_lo": i4(nt), "rt_hi": i4(nt), "scc": i4(nt), "scc_class": i4(nt),
             "steps": np.zeros(nt, dtype=AP_STEP_DTYPE),
             "cycle_off": np.zeros(LC_AP_MAX_CYCLES + 1, dtype=np.int64), "cycle_scc": i4(LC_AP_MAX_CYCLES),
         }
-        self.out = LcApOut(**{k: _ptr(v) for k, v in self.arrays.items()})
-        self.summary = LcApSummary()
-
-    def args(self):
-        return (_ptr(self.txns), len(self.txns), _ptr(self.mops), len(self.mops), _ptr(self.values),
-                len(self.values), ctypes.byref(self.out), ctypes.byref(self.summary))
+        return {k: _ptr(v) for k, v in self.arrays.items()}
 
     def result(self):
         """-> (a dict of the output arrays cut to their counts, the summary as a dict)."""
         s = {}
-        for f, _ in LcApSummary._fields_:
+        for f, _ in self.summary._fields_:
             v = getattr(self.summary, f)
             s[f] = list(v) if f == "n_class" else v
         a, nt, nm = self.arrays, len(self.txns), len(self.mops)
@@ -673,6 +666,23 @@ class _AppendCall:
                "steps": a["steps"][:n_steps], "cycle_off": a["cycle_off"][:s["n_cycles_returned"] + 1],
                "cycle_scc": a["cycle_scc"][:s["n_cycles_returned"]]}
         return out, s
+
+
+class _AppendCall(_TxnGraphCall):
+    """One lc_append_check(_host) call's arrays: the inputs made contiguous,
+    the outputs allocated as the header sizes them."""
+
+    def __init__(self, txns, mops, values):
+        self.txns = np.ascontiguousarray(txns, dtype=AP_TXN_DTYPE)
+        self.mops = np.ascontiguousarray(mops, dtype=AP_MOP_DTYPE)
+        self.values = np.ascontiguousarray(values, dtype=np.int64)
+        n_reads = int((self.mops["f"] == LC_AP_READ).sum())
+        self.out = LcApOut(**self._outputs(AP_KEY_DTYPE, n_reads + len(self.mops)))  # 2 reads + appends
+        self.summary = LcApSummary()
+
+    def args(self):
+        return (_ptr(self.txns), len(self.txns), _ptr(self.mops), len(self.mops), _ptr(self.values),
+                len(self.values), ctypes.byref(self.out), ctypes.byref(self.summary))
 
 
 def append_check_host(txns, mops, values):
@@ -694,7 +704,7 @@ def append_limits():
     return {f: getattr(s, f) for f, _ in LcApLimits._fields_}
 
 
-class _WrCall:
+class _WrCall(_TxnGraphCall):
     """One lc_wr_check(_host) call's arrays: the inputs made contiguous, the
     outputs allocated as the header sizes them, the edges with room for
     edge_cap (None: two per mop and 16, which a history without large reader
@@ -704,37 +714,13 @@ class _WrCall:
         self.txns = np.ascontiguousarray(txns, dtype=WR_TXN_DTYPE)
         self.mops = np.ascontiguousarray(mops, dtype=WR_MOP_DTYPE)
         self.flags = LC_WR_WFR_KEYS if wfr_keys else 0
-        nt, nm = max(len(self.txns), 1), max(len(self.mops), 1)
         self.edge_cap = 2 * len(self.mops) + 16 if edge_cap is None else int(edge_cap)
-        i4 = lambda n: np.zeros(n, dtype=np.int32)  # noqa: E731
-        self.arrays = {
-            "mop_flags": i4(nm), "txn_flags": i4(nt), "keys": np.zeros(nm, dtype=WR_KEY_DTYPE),
-            "edges": np.zeros(max(self.edge_cap, 1), dtype=WR_EDGE_DTYPE),
-            "byc": i4(nt), "rt_lo": i4(nt), "rt_hi": i4(nt), "scc": i4(nt), "scc_class": i4(nt),
-            "steps": np.zeros(nt, dtype=WR_STEP_DTYPE),
-            "cycle_off": np.zeros(LC_AP_MAX_CYCLES + 1, dtype=np.int64), "cycle_scc": i4(LC_AP_MAX_CYCLES),
-        }
-        self.out = LcWrOut(edge_cap=self.edge_cap, **{k: _ptr(v) for k, v in self.arrays.items()})
+        self.out = LcWrOut(edge_cap=self.edge_cap, **self._outputs(WR_KEY_DTYPE, self.edge_cap))
         self.summary = LcWrSummary()
 
     def args(self):
         return (_ptr(self.txns), len(self.txns), _ptr(self.mops), len(self.mops), self.flags,
                 ctypes.byref(self.out), ctypes.byref(self.summary))
-
-    def result(self):
-        """-> (a dict of the output arrays cut to their counts, the summary as a dict)."""
-        s = {}
-        for f, _ in LcWrSummary._fields_:
-            v = getattr(self.summary, f)
-            s[f] = list(v) if f == "n_class" else v
-        a, nt, nm = self.arrays, len(self.txns), len(self.mops)
-        n_steps = int(a["cycle_off"][s["n_cycles_returned"]])
-        out = {"mop_flags": a["mop_flags"][:nm], "txn_flags": a["txn_flags"][:nt], "keys": a["keys"][:s["n_keys"]],
-               "edges": a["edges"][:s["n_edges"]], "byc": a["byc"][:s["n_ok"]], "rt_lo": a["rt_lo"][:nt],
-               "rt_hi": a["rt_hi"][:nt], "scc": a["scc"][:nt], "scc_class": a["scc_class"][:nt],
-               "steps": a["steps"][:n_steps], "cycle_off": a["cycle_off"][:s["n_cycles_returned"] + 1],
-               "cycle_scc": a["cycle_scc"][:s["n_cycles_returned"]]}
-        return out, s
 
 
 def _wr_run(fn, who, error_text, txns, mops, wfr_keys, edge_cap):

@@ -1,63 +1,29 @@
 // append.h — what lc_append_check's host code (append_host.cpp, g++) and its
-// kernels (append.hip) share: the (key, element) hash, the host's
-// preparation pass, the host parts of the device call, and the kernels'
-// workspace and launchers.  The rules are include/lincheck_append.h's.
+// kernels (append.hip) share: the host's preparation pass, the host parts of
+// the device call, and the kernels' workspace and launcher.  The rules are
+// include/lincheck_append.h's; what lc_wr_check shares with them is
+// txngraph.h's.
 #pragma once
 #include <stdint.h>
 
 #include <vector>
 
-#include "../../../include/lincheck_append.h"
 #include "graph_host.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define LCAP_HD __host__ __device__ __forceinline__
-#else
-#define LCAP_HD inline
-#endif
+#include "txngraph.h"
 
 namespace lcap {
 
+using namespace lctg;  // the hash, the limits and the launchers both Elle checkers share
+
 constexpr int64_t kReserved = INT64_MIN;        // no key and no appended element
-constexpr int64_t kMaxPosition = 0x7FFFFFFF;    // positions are below 2^31 - 1
-constexpr int64_t kMaxMops = 0x7FFFFFFF;
-// the device call's bound on n_mops: the key table (table_capacity) then has at most 2^30 slots, and a slot
-// index is an int32 (mop_kslot, the slot list of the key records)
-constexpr int64_t kMaxDeviceMops = int64_t(1) << 29;
 constexpr int64_t kDefaultMaxPayload = int64_t(1) << 30;
-constexpr int kCounterStride = 16;              // in int64: the waves' counters lie 128 B apart
-constexpr int kCounterShards = 32;
 constexpr int kCounters = 6;                    // duplicate, g1a, phantom, g1b, internal, slow reads
-constexpr int kItemChunk = 4096;                // work items of one workgroup iteration of the item pass
-
-LCAP_HD uint64_t mix64(uint64_t x) {  // murmur3's 64-bit finaliser
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  x *= 0xC4CEB9FE1A85EC53ull;
-  x ^= x >> 33;
-  return x;
-}
-
-// The writer table's hash of a (key, element) pair: the slot is its low bits,
-// the slot's tag its high 32.
-LCAP_HD uint64_t hash_pair(int64_t key, int64_t element) {
-  return mix64(mix64((uint64_t)key) + 0x9E3779B97F4A7C15ull + (uint64_t)element);
-}
-
-// Both tables: a power of two of at least 2 n, at least 64.
-inline uint64_t table_capacity(int64_t n) {
-  uint64_t cap = 64;
-  while (cap < 2 * (uint64_t)n) cap <<= 1;
-  return cap;
-}
 
 // The longest-read word of a key: (len, ~read ordinal), larger is better;
 // 0: never read.
-LCAP_HD uint64_t pack_best(int32_t len, int32_t r) { return ((uint64_t)(uint32_t)len << 32) | (uint32_t)~r; }
-LCAP_HD int32_t best_read(uint64_t b) { return (int32_t)~(uint32_t)b; }
-LCAP_HD int32_t best_len(uint64_t b) { return (int32_t)(b >> 32); }
+LCTG_HD uint64_t pack_best(int32_t len, int32_t r) { return ((uint64_t)(uint32_t)len << 32) | (uint32_t)~r; }
+LCTG_HD int32_t best_read(uint64_t b) { return (int32_t)~(uint32_t)b; }
+LCTG_HD int32_t best_len(uint64_t b) { return (int32_t)(b >> 32); }
 
 // What one pass over the input gives the host (append_host.cpp, prepare):
 // the contract checked, and the arrays both paths index by.  The "real" reads
@@ -145,25 +111,11 @@ constexpr int32_t kKeyTwoPhantoms = 1 << 30;
 constexpr int32_t kTxnSlow = 1 << 30;
 
 // Tables filled and built, longest reads taken, the item pass, the read/txn
-// pass, the ww slots and the key records: everything before the edge sort.
-// kslots has kcap entries; *d_n_keys receives the number of key records.
-size_t key_temp_bytes(uint64_t kcap);
+// pass, the ww slots and the key records: everything before the edge select.
+// kslots has kcap entries; *d_n_keys receives the number of key records; temp
+// has key_temp_bytes(kcap).
 hipError_t launch_rules(const Ws &w, int32_t *kslots, int64_t *d_n_keys, void *temp, size_t temp_bytes,
                         hipStream_t st);
-
-// Edge compaction, sort and unique; real time.  Temporary storage is the
-// caller's: *_bytes(n) say how much a call over n records needs.
-size_t edge_temp_bytes(int64_t n_slots);
-hipError_t launch_edge_select(const Ws &w, lc_ap_edge *dst, int64_t *d_count, void *temp, size_t temp_bytes,
-                              hipStream_t st);
-hipError_t launch_edge_sort(lc_ap_edge *src, lc_ap_edge *dst, int64_t n, int64_t *d_count, void *temp,
-                            size_t temp_bytes, hipStream_t st);
-size_t rt_temp_bytes(int64_t n_txns);
-// byc (n_ok of them), rt_lo, rt_hi on the device; the int32 arrays have
-// n_txns entries each, d_count is one scratch word.
-hipError_t launch_real_time(const Ws &w, int64_t n_ok, int32_t *ok_idx, int32_t *ok_comp, int32_t *byc,
-                            int32_t *comp_sorted, int32_t *pm, int32_t *rt_lo, int32_t *rt_hi, int64_t *d_count,
-                            void *temp, size_t temp_bytes, hipStream_t st);
 #endif
 
 }  // namespace lcap

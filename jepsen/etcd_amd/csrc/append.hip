@@ -1,10 +1,8 @@
 // append.hip — the kernels of lc_append_check (include/lincheck_append.h):
 // rules 1 to 6 over flat arrays.  Rule 7 is the host's (append_host.cpp).
 //
-//  ap_mop_kernel (one thread per mop): the mop's key into the key table (a
-//    64-bit compare-and-swap on the key, linear probing); an append into the
-//    writer table, whose word is (hash tag << 32) | mop — the pair itself is
-//    read from the mops, so one 64-bit word decides a 128-bit key; a second
+//  ap_mop_kernel (one thread per mop): the mop's key into the key table; an
+//    append into the writer table, a pair table over (key, element); a second
 //    insertion of one pair raises status[0].  Also rule 1's "last append".
 //  ap_best_kernel (one thread per real read): one 64-bit atomicMax of
 //    (len, ~read) on its key's slot.
@@ -24,72 +22,27 @@
 //    counters 128 B apart.
 //  ap_item_kernel<1> (the same enumeration, once the keys' flags are final):
 //    the ww slots, one per order position.
-//  ap_keys_kernel: rocprim select lists the key table's occupied slots; a
-//    thread per listed slot writes its record.
-//  Edges: rocprim select, merge_sort by (from, to, type, key), unique — the
-//    result does not depend on which slot an edge came from.  Real time:
-//    rocprim select / radix sort / prefix max, then two binary searches per txn.
+//  ap_keys_kernel: a thread per occupied slot of the key table, which
+//    txngraph.hip's launch_key_slots lists, writes its record.
+//  The edges' select, sort and unique and real time (rule 6) are
+//  txngraph.hip's, the two table formats txngraph_dev.h's.
 //
 // Every loop is bounded by a txn, mop, read, payload or table count; no
 // workgroup waits for another; results leave through vector stores.
-#include <rocprim/device/device_merge_sort.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#include <algorithm>
-
 #include "append.h"
+#include "txngraph_dev.h"
 
 namespace lcap {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxGrid = 256 * 8;
-constexpr unsigned long long kEmptyWord = ~0ull;
 constexpr uint32_t kNoIndex = 0xFFFFFFFFu;  // first_* and stamps on the device: unsigned, so -1 once cast
-constexpr int64_t kKeyXor = 0x7FFFFFFFFFFFFFFFll;  // a stored key is key ^ this: the reserved key reads ~0
-
-int grid_for(int64_t items, int64_t per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < kMaxGrid ? g : kMaxGrid);
-}
-
-// The writer of (key, element): its mop and its slot, or -1.
-__device__ __forceinline__ int32_t find_writer(const Ws &w, int64_t key, int64_t element, uint64_t *slot) {
-  const uint64_t h = hash_pair(key, element);
-  uint64_t s = h & (w.wcap - 1);
-  for (uint64_t p = 0; p < w.wcap; p++) {
-    const unsigned long long word = w.wtab[s];
-    if (word == kEmptyWord) return -1;
-    if ((word >> 32) == (h >> 32)) {
-      const int32_t m = (int32_t)(uint32_t)word;
-      if (w.mops[m].key == key && w.mops[m].value == element) {
-        *slot = s;
-        return m;
-      }
-    }
-    s = (s + 1) & (w.wcap - 1);
-  }
-  return -1;
-}
 
 __global__ __launch_bounds__(kThreads) void ap_mop_kernel(Ws w) {
   unsigned long long *ktab = reinterpret_cast<unsigned long long *>(w.ktab);
   for (int64_t m = blockIdx.x * (int64_t)kThreads + threadIdx.x; m < w.n_mops; m += (int64_t)gridDim.x * kThreads) {
     const lc_ap_mop o = w.mops[m];
-    const unsigned long long enc = (unsigned long long)(o.key ^ kKeyXor);
-    uint64_t ks = mix64((uint64_t)o.key) & (w.kcap - 1);
-    for (uint64_t p = 0; p < w.kcap; p++) {
-      const unsigned long long old = atomicCAS(&ktab[ks], kEmptyWord, enc);
-      if (old == kEmptyWord || old == enc) break;
-      ks = (ks + 1) & (w.kcap - 1);
-    }
-    w.mop_kslot[m] = (int32_t)ks;
+    w.mop_kslot[m] = key_claim(ktab, w.kcap, o.key);
     if (o.f != LC_AP_APPEND) continue;
     const lc_ap_txn x = w.txns[w.mop_txn[m]];
     uint8_t last = 1;
@@ -99,21 +52,10 @@ __global__ __launch_bounds__(kThreads) void ap_mop_kernel(Ws w) {
         break;
       }
     w.mop_last[m] = last;
-    const uint64_t h = hash_pair(o.key, o.value);
-    const unsigned long long word = ((h >> 32) << 32) | (unsigned long long)(uint32_t)m;
-    uint64_t s = h & (w.wcap - 1);
-    for (uint64_t p = 0; p < w.wcap; p++) {
-      const unsigned long long old = atomicCAS(&w.wtab[s], kEmptyWord, word);
-      if (old == kEmptyWord) break;
-      if ((old >> 32) == (h >> 32)) {
-        const int32_t om = (int32_t)(uint32_t)old;
-        if (w.mops[om].key == o.key && w.mops[om].value == o.value) {  // two appends of one pair
-          w.status[1] = (int32_t)m;
-          w.status[0] = 1;
-          break;
-        }
-      }
-      s = (s + 1) & (w.wcap - 1);
+    bool inserted;  // found, not inserted: two appends of one pair
+    if (pair_claim(w.wtab, w.wcap, w.mops, m, o.key, o.value, &inserted) >= 0 && !inserted) {
+      w.status[1] = (int32_t)m;
+      w.status[0] = 1;
     }
   }
 }
@@ -174,8 +116,8 @@ __global__ __launch_bounds__(kThreads) void ap_item_kernel(Ws w) {
         }
         continue;
       }
-      uint64_t s = 0;
-      const int32_t wm = find_writer(w, o.key, v, &s);
+      int32_t wm = -1;  // the entry's writer: its slot and its mop
+      const int32_t s = pair_find(w.wtab, w.wcap, w.mops, o.key, v, &wm);
       w.ord_w[i] = wm;
       if (wm < 0) {
         if (atomicMin(&kfirst[3 * (int64_t)ks + 2], (uint32_t)j) != kNoIndex) atomicOr(&w.kflags[ks], kKeyTwoPhantoms);
@@ -190,7 +132,6 @@ __global__ __launch_bounds__(kThreads) void ap_item_kernel(Ws w) {
 }
 
 __global__ __launch_bounds__(kThreads) void ap_txn_kernel(Ws w) {
-  __shared__ long long s_cnt[kWaves][kCounters];
   const int32_t *kfirst = w.kfirst;
   long long cnt[kCounters] = {0, 0, 0, 0, 0, 0};
   for (int64_t t = blockIdx.x * (int64_t)kThreads + threadIdx.x; t < w.n_txns; t += (int64_t)gridDim.x * kThreads) {
@@ -264,20 +205,7 @@ __global__ __launch_bounds__(kThreads) void ap_txn_kernel(Ws w) {
     }
     w.txn_flags[t] = tf | (slow ? kTxnSlow : 0);
   }
-  for (int b = 0; b < kCounters; b++) {
-    long long v = cnt[b];
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][b] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kCounters) {
-    long long v = 0;
-    for (int i = 0; i < kWaves; i++) v += s_cnt[i][threadIdx.x];
-    if (v)
-      atomicAdd(reinterpret_cast<unsigned long long *>(
-                    &w.counters[((int64_t)threadIdx.x * kCounterShards + blockIdx.x % kCounterShards) * kCounterStride]),
-                (unsigned long long)v);
-  }
+  flush_counters(cnt, w.counters);
 }
 
 __global__ __launch_bounds__(kThreads) void ap_keys_kernel(Ws w, const int32_t *__restrict__ kslots,
@@ -301,79 +229,7 @@ __global__ __launch_bounds__(kThreads) void ap_keys_kernel(Ws w, const int32_t *
   }
 }
 
-struct KeySet {
-  const int64_t *ktab;
-  __host__ __device__ bool operator()(int32_t s) const { return ktab[s] != -1; }
-};
-struct EdgeSet {
-  __host__ __device__ bool operator()(const lc_ap_edge &e) const { return e.from >= 0; }
-};
-struct EdgeLess {
-  __host__ __device__ bool operator()(const lc_ap_edge &a, const lc_ap_edge &b) const {
-    if (a.from != b.from) return a.from < b.from;
-    if (a.to != b.to) return a.to < b.to;
-    if (a.type != b.type) return a.type < b.type;
-    return a.key < b.key;
-  }
-};
-struct EdgeSame {
-  __host__ __device__ bool operator()(const lc_ap_edge &a, const lc_ap_edge &b) const {
-    return a.from == b.from && a.to == b.to && a.type == b.type && a.key == b.key;
-  }
-};
-struct IsOk {
-  const lc_ap_txn *txns;
-  __host__ __device__ bool operator()(int32_t t) const { return txns[t].type == LC_AP_OK; }
-};
-struct MaxOp {
-  __host__ __device__ int32_t operator()(int32_t a, int32_t b) const { return a > b ? a : b; }
-};
-
-// kind 0: out[i] = comp_pos of txn idx[i]; kind 1: its inv_pos.
-template <int kKind>
-__global__ __launch_bounds__(kThreads) void ap_gather_kernel(const lc_ap_txn *__restrict__ txns,
-                                                             const int32_t *__restrict__ idx, int64_t n,
-                                                             int32_t *__restrict__ out) {
-  for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
-    out[i] = kKind ? txns[idx[i]].inv_pos : txns[idx[i]].comp_pos;
-}
-
-// The number of entries of comp[0, n) below x.
-__device__ __forceinline__ int64_t count_below(const int32_t *__restrict__ comp, int64_t n, int32_t x) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (comp[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(kThreads) void ap_rt_kernel(const lc_ap_txn *__restrict__ txns, int64_t n_txns,
-                                                         const int32_t *__restrict__ comp,
-                                                         const int32_t *__restrict__ pm, int64_t n_ok,
-                                                         int32_t *__restrict__ rt_lo, int32_t *__restrict__ rt_hi) {
-  for (int64_t t = blockIdx.x * (int64_t)kThreads + threadIdx.x; t < n_txns; t += (int64_t)gridDim.x * kThreads) {
-    int32_t lo = 0, hi = 0;
-    if (txns[t].type != LC_AP_FAIL) {
-      hi = (int32_t)count_below(comp, n_ok, txns[t].inv_pos);
-      // positions are distinct: above m(B) is at or above m(B) + 1
-      lo = hi ? (int32_t)count_below(comp, n_ok, pm[hi - 1] + 1) : 0;
-    }
-    rt_lo[t] = lo;
-    rt_hi[t] = hi;
-  }
-}
-
 }  // namespace
-
-size_t key_temp_bytes(uint64_t kcap) {
-  size_t a = 0;
-  int32_t *p = nullptr;
-  int64_t *cnt = nullptr;
-  (void)rocprim::select(nullptr, a, rocprim::counting_iterator<int32_t>(0), p, cnt, (size_t)kcap, KeySet{nullptr});
-  return a;
-}
 
 hipError_t launch_rules(const Ws &w, int32_t *kslots, int64_t *d_n_keys, void *temp, size_t temp_bytes,
                         hipStream_t st) {
@@ -383,69 +239,9 @@ hipError_t launch_rules(const Ws &w, int32_t *kslots, int64_t *d_n_keys, void *t
   ap_txn_kernel<<<grid_for(w.n_txns, kThreads), kThreads, 0, st>>>(w);
   if (w.n_work > 0) ap_item_kernel<1><<<grid_for(w.n_work, kItemChunk), kThreads, 0, st>>>(w);
   // the occupied slots of the key table, in slot order; at most n_mops of them
-  size_t bytes = temp_bytes;
-  hipError_t e = rocprim::select(temp, bytes, rocprim::counting_iterator<int32_t>(0), kslots, d_n_keys,
-                                 (size_t)w.kcap, KeySet{w.ktab}, st);
+  hipError_t e = launch_key_slots(w.ktab, w.kcap, kslots, d_n_keys, temp, temp_bytes, st);
   if (e != hipSuccess) return e;
   ap_keys_kernel<<<grid_for(w.n_mops, kThreads), kThreads, 0, st>>>(w, kslots, d_n_keys);
-  return hipGetLastError();
-}
-
-size_t edge_temp_bytes(int64_t n_slots) {
-  size_t a = 0, b = 0, c = 0;
-  lc_ap_edge *e = nullptr;
-  int64_t *cnt = nullptr;
-  const size_t n = (size_t)(n_slots > 0 ? n_slots : 1);
-  (void)rocprim::select(nullptr, a, e, e, cnt, n, EdgeSet());
-  (void)rocprim::merge_sort(nullptr, b, e, e, n, EdgeLess());
-  (void)rocprim::unique(nullptr, c, e, e, cnt, n, EdgeSame());
-  return std::max(a, std::max(b, c));
-}
-
-hipError_t launch_edge_select(const Ws &w, lc_ap_edge *dst, int64_t *d_count, void *temp, size_t temp_bytes,
-                              hipStream_t st) {
-  return rocprim::select(temp, temp_bytes, w.slots, dst, d_count, (size_t)(2 * w.n_real + w.n_work), EdgeSet(), st);
-}
-
-hipError_t launch_edge_sort(lc_ap_edge *src, lc_ap_edge *dst, int64_t n, int64_t *d_count, void *temp,
-                            size_t temp_bytes, hipStream_t st) {
-  size_t bytes = temp_bytes;
-  hipError_t e = rocprim::merge_sort(temp, bytes, src, dst, (size_t)n, EdgeLess(), st);
-  if (e != hipSuccess) return e;
-  bytes = temp_bytes;
-  return rocprim::unique(temp, bytes, dst, src, d_count, (size_t)n, EdgeSame(), st);
-}
-
-size_t rt_temp_bytes(int64_t n_txns) {
-  size_t a = 0, b = 0, c = 0;
-  int32_t *p = nullptr;
-  int64_t *cnt = nullptr;
-  const size_t n = (size_t)(n_txns > 0 ? n_txns : 1);
-  (void)rocprim::select(nullptr, a, rocprim::counting_iterator<int32_t>(0), p, cnt, n, IsOk{nullptr});
-  (void)rocprim::radix_sort_pairs(nullptr, b, p, p, p, p, n);
-  (void)rocprim::inclusive_scan(nullptr, c, p, p, n, MaxOp());
-  return std::max(a, std::max(b, c));
-}
-
-hipError_t launch_real_time(const Ws &w, int64_t n_ok, int32_t *ok_idx, int32_t *ok_comp, int32_t *byc,
-                            int32_t *comp_sorted, int32_t *pm, int32_t *rt_lo, int32_t *rt_hi, int64_t *d_count,
-                            void *temp, size_t temp_bytes, hipStream_t st) {
-  if (n_ok > 0) {
-    size_t bytes = temp_bytes;  // (the count select writes is the host's n_ok)
-    hipError_t e = rocprim::select(temp, bytes, rocprim::counting_iterator<int32_t>(0), ok_idx, d_count,
-                                   (size_t)w.n_txns, IsOk{w.txns}, st);
-    if (e != hipSuccess) return e;
-    ap_gather_kernel<0><<<grid_for(n_ok, kThreads), kThreads, 0, st>>>(w.txns, ok_idx, n_ok, ok_comp);
-    bytes = temp_bytes;
-    e = rocprim::radix_sort_pairs(temp, bytes, ok_comp, comp_sorted, ok_idx, byc, (size_t)n_ok, 0, 32, st);
-    if (e != hipSuccess) return e;
-    ap_gather_kernel<1><<<grid_for(n_ok, kThreads), kThreads, 0, st>>>(w.txns, byc, n_ok, ok_comp);
-    bytes = temp_bytes;
-    e = rocprim::inclusive_scan(temp, bytes, ok_comp, pm, (size_t)n_ok, MaxOp(), st);
-    if (e != hipSuccess) return e;
-  }
-  ap_rt_kernel<<<grid_for(w.n_txns, kThreads), kThreads, 0, st>>>(w.txns, w.n_txns, comp_sorted, pm, n_ok, rt_lo,
-                                                                 rt_hi);
   return hipGetLastError();
 }
 

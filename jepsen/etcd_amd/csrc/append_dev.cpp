@@ -1,10 +1,9 @@
 // append_dev.cpp — lc_append_check's driver (include/lincheck_append.h): the
 // arrays copied to the context's first device; rules 1 to 6 there
-// (append.hip); the reads the device left open, rule 7 and the summary on the
+// (append.hip, txngraph.hip); the reads the device left open, rule 7 and the summary on the
 // host (append_host.cpp).
 #include <algorithm>
 #include <chrono>
-#include <new>
 #include <string>
 
 #include "append.h"
@@ -13,6 +12,13 @@
 using namespace lcrt;
 
 namespace {
+
+constexpr size_t kCountersLen = lcap::kCounters * lcap::kCounterShards * lcap::kCounterStride;
+struct Pinned {
+  int32_t status[4];
+  int64_t count[4];  // set slots, edges, (OK txns), keys
+  int64_t counters[kCountersLen];
+};
 
 int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
                   const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
@@ -36,15 +42,12 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
     set_err(c, "lc_append_check: more mops than lc_append_limits' max_mops");
     return -E2BIG;
   }
-  ApState &s = c->aps;
+  SideState &s = c->aps;
   hipStream_t st;
-  if (int e = side_begin(c, &st)) return e;
-  constexpr size_t kCountersLen = lcap::kCounters * lcap::kCounterShards * lcap::kCounterStride;
-  constexpr size_t kSmall = 6 + kCountersLen;  // in int64: 4 status words, 4 counts, the counters
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2, &s.k0, &s.k1, &s.k2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
-  }
+  if (int e = side_begin(c, s, 6, sizeof(Pinned), &st)) return e;
+  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
+  const hipEvent_t e0 = s.ev[0], e1 = s.ev[1], e2 = s.ev[2], k0 = s.ev[3], k1 = s.ev[4], k2 = s.ev[5];
+  Pinned &h = *s.words<Pinned>();
   const uint64_t wcap = lcap::table_capacity(p.n_appends), kcap = lcap::table_capacity(n_mops);
   const size_t n_slots = 2 * nr + (size_t)n_work, n_edge_room = 2 * nr + (size_t)p.n_appends;
   const size_t temp_bytes = std::max({lcap::edge_temp_bytes((int64_t)n_slots), lcap::rt_temp_bytes(n_txns),
@@ -59,7 +62,8 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   // beside w: the edge lists, the key table's occupied slots, the counts (set
   // slots, edges, OK txns, keys), real time's arrays, rocprim's temporary storage
   lc_ap_edge *d_edges_a = nullptr, *d_edges_b = nullptr;
-  int32_t *d_kslots = nullptr, *rt = nullptr;
+  int32_t *d_kslots = nullptr;
+  lcap::RtArrays rt{};
   int64_t *d_count = nullptr;
   uint8_t *d_temp = nullptr;
   auto layout = [&](Carver ws) {
@@ -92,13 +96,13 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
     w.counters = ws.take<int64_t>(kCountersLen);
     d_count = ws.take<int64_t>(4);
     w.status = ws.take<int32_t>(4);
-    rt = ws.take<int32_t>(7 * nt);  // ok_idx, ok_comp, byc, comp_sorted, pm, rt_lo, rt_hi: n_txns each
+    rt.carve(ws, nt);
     d_temp = ws.take<uint8_t>(temp_bytes);
     return ws.size;
   };
   if (int e = ensure(c, s.arena, layout(Carver{}))) return e;
   layout(Carver{s.arena.p});
-  HIP_TRY(c, hipEventRecord(s.e0, st));
+  HIP_TRY(c, hipEventRecord(e0, st));
   HIP_TRY(c, hipMemcpyAsync(writable(w.txns), txns, sizeof(lc_ap_txn) * nt, hipMemcpyHostToDevice, st));
   if (nm) {
     HIP_TRY(c, hipMemcpyAsync(writable(w.mops), mops, sizeof(lc_ap_mop) * nm, hipMemcpyHostToDevice, st));
@@ -114,7 +118,7 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
                             st));
   HIP_TRY(c, hipMemcpyAsync(writable(w.work_off), p.work_off.data(), sizeof(int64_t) * (nr + 1),
                             hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
+  HIP_TRY(c, hipEventRecord(e1, st));
   // nothing of an earlier call survives: empty tables (every empty word is
   // all ones), no flags, no edge slots, no counts
   HIP_TRY(c, hipMemsetAsync(w.wtab, 0xFF, sizeof(unsigned long long) * wcap, st));
@@ -131,42 +135,39 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   HIP_TRY(c, hipMemsetAsync(w.counters, 0, sizeof(int64_t) * kCountersLen, st));
   HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(int64_t) * 4, st));
   HIP_TRY(c, hipMemsetAsync(w.status, 0, sizeof(int32_t) * 4, st));
-  int32_t *d_byc = rt + 2 * nt, *d_lo = rt + 5 * nt, *d_hi = rt + 6 * nt;
-  HIP_TRY(c, hipEventRecord(s.k0, st));
+  HIP_TRY(c, hipEventRecord(k0, st));
   if (nm) HIP_TRY(c, lcap::launch_rules(w, d_kslots, d_count + 3, d_temp, temp_bytes, st));
-  if (n_slots) HIP_TRY(c, lcap::launch_edge_select(w, d_edges_a, d_count, d_temp, temp_bytes, st));
-  HIP_TRY(c, lcap::launch_real_time(w, p.n_ok, rt, rt + nt, d_byc, rt + 3 * nt, rt + 4 * nt, d_lo, d_hi, d_count + 2,
-                                    d_temp, temp_bytes, st));
-  HIP_TRY(c, hipEventRecord(s.k1, st));
-  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
-  int64_t *h_count = s.h_small + 2, *h_counters = s.h_small + 6;  // counts: set slots, edges, (OK txns), keys
-  HIP_TRY(c, hipMemcpyAsync(h_status, w.status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_count, d_count, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_counters, w.counters, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
+  if (n_slots)
+    HIP_TRY(c, lcap::launch_edge_select(w.slots, (int64_t)n_slots, d_edges_a, d_count, d_temp, temp_bytes, st));
+  HIP_TRY(c, lcap::launch_real_time(w.txns, n_txns, p.n_ok, rt, d_count + 2, d_temp, temp_bytes, st));
+  HIP_TRY(c, hipEventRecord(k1, st));
+  HIP_TRY(c, hipMemcpyAsync(h.status, w.status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h.count, d_count, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h.counters, w.counters, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  if (h_status[0]) {
-    set_err(c, "lc_append_check: two appends of one (key, element) (mop " + std::to_string(h_status[1]) + " is one)");
+  if (h.status[0]) {
+    set_err(c, "lc_append_check: two appends of one (key, element) (mop " + std::to_string(h.status[1]) + " is one)");
     return -EINVAL;
   }
-  const int64_t n_sel = h_count[0], n_keys = h_count[3];
+  const int64_t n_sel = h.count[0], n_keys = h.count[3];
   if (n_sel > (int64_t)n_edge_room || n_keys > n_mops) {  // (more edges than rule 5 allows: a bug, not an input)
     set_err(c, "lc_append_check: inconsistent edge or key count");
     return -EIO;
   }
-  h_count[1] = 0;
-  HIP_TRY(c, hipEventRecord(s.k2, st));
+  h.count[1] = 0;
+  HIP_TRY(c, hipEventRecord(k2, st));
   if (n_sel > 0) HIP_TRY(c, lcap::launch_edge_sort(d_edges_a, d_edges_b, n_sel, d_count + 1, d_temp, temp_bytes, st));
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  if (n_sel > 0) HIP_TRY(c, hipMemcpyAsync(h_count + 1, d_count + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipEventRecord(e2, st));
+  if (n_sel > 0) HIP_TRY(c, hipMemcpyAsync(h.count + 1, d_count + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   if (nm) HIP_TRY(c, hipMemcpyAsync(out->mop_flags, w.mop_flags, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(out->txn_flags, w.txn_flags, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
   if (n_keys)
     HIP_TRY(c, hipMemcpyAsync(out->keys, w.keys, sizeof(lc_ap_key) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
-  if (p.n_ok) HIP_TRY(c, hipMemcpyAsync(out->byc, d_byc, sizeof(int32_t) * (size_t)p.n_ok, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->rt_lo, d_lo, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->rt_hi, d_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  if (p.n_ok) HIP_TRY(c, hipMemcpyAsync(out->byc, rt.byc, sizeof(int32_t) * (size_t)p.n_ok, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->rt_lo, rt.rt_lo, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->rt_hi, rt.rt_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  const int64_t n_edges = h_count[1];
+  const int64_t n_edges = h.count[1];
   if (n_edges > 0) {  // only the unique edges reach the caller
     HIP_TRY(c, hipMemcpyAsync(out->edges, d_edges_a, sizeof(lc_ap_edge) * (size_t)n_edges, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
@@ -182,10 +183,8 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   }
   // exact but not fast: the txns the device left open (a history without
   // non-prefix reads and twice-phantom orders has none)
-  int64_t counts[lcap::kCounters] = {0}, n_nonprefix = 0;
-  for (int b = 0; b < lcap::kCounters; b++)
-    for (int i = 0; i < lcap::kCounterShards; i++)
-      counts[b] += h_counters[((size_t)b * lcap::kCounterShards + i) * lcap::kCounterStride];
+  int64_t counts[lcap::kCounters], n_nonprefix = 0;
+  for (int b = 0; b < lcap::kCounters; b++) counts[b] = lcap::sum_counters(h.counters, b);
   const int64_t n_slow = counts[5];
   if (n_slow) {
     lcap::Writers wr;
@@ -205,9 +204,9 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   lc_ap_summary sm;
   lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm);
   sm.n_slow_reads = n_slow;
-  sm.h2d_ms = elapsed_ms(s.e0, s.e1);
-  sm.kernel_ms = elapsed_ms(s.k0, s.k1);
-  sm.kernel_ms += elapsed_ms(s.k2, s.e2);
+  sm.h2d_ms = elapsed_ms(e0, e1);
+  sm.kernel_ms = elapsed_ms(k0, k1);
+  sm.kernel_ms += elapsed_ms(k2, e2);
   sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = sm;
   return 0;
@@ -215,21 +214,10 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
 
 }  // namespace
 
-void lcrt::release(ApState &s) {
-  if (s.arena.p) (void)hipFree(s.arena.p);
-  if (s.h_small) (void)hipHostFree(s.h_small);
-  for (hipEvent_t e : {s.e0, s.e1, s.e2, s.k0, s.k1, s.k2})
-    if (e) (void)hipEventDestroy(e);
-}
-
 extern "C" int lc_append_check(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops,
                                int64_t n_mops, const int64_t *values, int64_t n_values, const lc_ap_out *out,
                                lc_ap_summary *sum) {
   if (!c) return -EINVAL;
-  try {
-    return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum);
-  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
-    set_err(c, "lc_append_check: out of host memory");
-    return -ENOMEM;
-  }
+  return no_bad_alloc(c, "lc_append_check",
+                      [&] { return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum); });
 }

@@ -17,25 +17,6 @@
 
 namespace lcap {
 
-namespace {
-
-struct PairHash {
-  size_t operator()(const std::pair<int64_t, int64_t> &p) const { return (size_t)hash_pair(p.first, p.second); }
-};
-
-bool edge_less(const lc_ap_edge &a, const lc_ap_edge &b) {
-  if (a.from != b.from) return a.from < b.from;
-  if (a.to != b.to) return a.to < b.to;
-  if (a.type != b.type) return a.type < b.type;
-  return a.key < b.key;
-}
-
-bool edge_same(const lc_ap_edge &a, const lc_ap_edge &b) {
-  return a.from == b.from && a.to == b.to && a.type == b.type && a.key == b.key;
-}
-
-}  // namespace
-
 struct Writers::Impl {
   std::unordered_map<std::pair<int64_t, int64_t>, int32_t, PairHash> map;
 };
@@ -74,26 +55,15 @@ int prepare(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_
       (n_values > 0 && !values))
     LCAP_BAD("null array or negative count");
   if (n_mops >= kMaxMops || n_txns >= kMaxMops) LCAP_BAD("2^31 - 1 or more txns or mops");
-  if (!out || !out->mop_flags || !out->txn_flags || !out->keys || !out->edges || !out->byc || !out->rt_lo ||
-      !out->rt_hi || !out->scc || !out->scc_class || !out->steps || !out->cycle_off || !out->cycle_scc)
-    LCAP_BAD("null out");
+  if (null_out(out)) LCAP_BAD("null out");
   p->mop_txn.resize((size_t)n_mops);
   p->txn_r0.resize((size_t)n_txns + 1);
   p->work_off.assign(1, 0);
   int64_t next = 0, prev_inv = -1;
   for (int64_t t = 0; t < n_txns; t++) {
     const lc_ap_txn &x = txns[t];
-    if (x.inv_pos <= prev_inv || x.inv_pos >= kMaxPosition) LCAP_BAD("txns not strictly ascending by inv_pos");
+    if (const char *bad = check_txn(x, prev_inv, next, n_mops)) LCAP_BAD(bad);
     prev_inv = x.inv_pos;
-    if (x.type == LC_AP_INFO) {
-      if (x.comp_pos != -1) LCAP_BAD("an INFO txn with a comp_pos");
-    } else if (x.type == LC_AP_OK || x.type == LC_AP_FAIL) {
-      if (x.comp_pos <= x.inv_pos || x.comp_pos >= kMaxPosition) LCAP_BAD("comp_pos not above inv_pos");
-    } else {
-      LCAP_BAD("unknown txn type");
-    }
-    if (x.mop_off != next || x.mop_len < 0 || x.mop_len > n_mops - next)
-      LCAP_BAD("the txns' mop ranges do not tile the mops in order");
     p->txn_r0[(size_t)t] = (int32_t)p->rd_mop.size();
     for (int64_t m = next; m < next + x.mop_len; m++) {
       const lc_ap_mop &o = mops[m];

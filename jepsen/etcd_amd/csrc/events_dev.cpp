@@ -12,7 +12,7 @@ using namespace lcrt;
 
 namespace {
 
-// On return the stream has drained, s.h_status holds the call's counts, and
+// On return the stream has drained, the pinned words hold the call's counts, and
 // the records are in s.w's ops32 / completion / key_off / key_base.
 int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_events, int64_t n_keys) {
   const std::string name(who);
@@ -27,11 +27,9 @@ int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_even
     return -EINVAL;
   }
   hipStream_t st;
-  if (int e = side_begin(c, &st)) return e;
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_status), sizeof(lcev::Status), 0));
-  }
+  if (int e = side_begin(c, s, 3, sizeof(lcev::Status), &st)) return e;
+  const hipEvent_t e0 = s.ev[0], e1 = s.ev[1], e2 = s.ev[2];
+  lcev::Status *h_status = s.words<lcev::Status>();
   const size_t n = (size_t)n_events, k = (size_t)n_keys;
   lcev::Ws &w = s.w;
   w = lcev::Ws{};
@@ -57,9 +55,9 @@ int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_even
   };
   if (int e = ensure(c, s.arena, layout(Carver{}))) return e;
   layout(Carver{s.arena.p});
-  HIP_TRY(c, hipEventRecord(s.e0, st));
+  HIP_TRY(c, hipEventRecord(e0, st));
   if (n) HIP_TRY(c, hipMemcpyAsync(writable(w.ev), ev, sizeof(lc_event) * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
+  HIP_TRY(c, hipEventRecord(e1, st));
   // no counter of an earlier call, larger or smaller, survives
   HIP_TRY(c, hipMemsetAsync(w.status, 0, sizeof(lcev::Status), st));
   if (k > 1) {
@@ -67,12 +65,12 @@ int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_even
     HIP_TRY(c, hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * k, st));
   }
   HIP_TRY(c, lcev::launch_events(w, st));
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  HIP_TRY(c, hipMemcpyAsync(s.h_status, w.status, sizeof(lcev::Status), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipEventRecord(e2, st));
+  HIP_TRY(c, hipMemcpyAsync(h_status, w.status, sizeof(lcev::Status), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  s.stats.h2d_ms = elapsed_ms(s.e0, s.e1);
-  s.stats.split_ms = elapsed_ms(s.e1, s.e2);
-  const lcev::Status &h = *s.h_status;
+  s.stats.h2d_ms = elapsed_ms(e0, e1);
+  s.stats.split_ms = elapsed_ms(e1, e2);
+  const lcev::Status &h = *s.words<lcev::Status>();
   s.stats.n_events = n_events;
   s.stats.n_client = h.n_client;
   s.stats.n_ops = h.n_ops;
@@ -90,7 +88,7 @@ int events_device(lc_ctx *c, const char *who, const lc_event *ev, int64_t n_even
 // The packed records of the last events_device call into the caller's arrays.
 int events_copy_out(lc_ctx *c, const char *who, int64_t n_keys, lc_events_out *out) {
   EvState &s = c->evs;
-  const lcev::Status &h = *s.h_status;
+  const lcev::Status &h = *s.words<lcev::Status>();
   if (!out->key_off || (n_keys > 0 && !out->key_base) || out->cap < h.n_invoke ||
       (h.n_ops > 0 && (!out->ops32 || !out->completion))) {
     set_err(c, std::string(who) + ": lc_events_out: a null array, or cap below the number of invokes");
@@ -121,7 +119,7 @@ int events_check(lc_ctx *c, int64_t n_keys, const lc_opts *opts, lc_key_result *
     set_err(c, "lc_check_events: null out");
     return -EINVAL;
   }
-  const size_t k = (size_t)n_keys, m = (size_t)s.h_status->n_ops;
+  const size_t k = (size_t)n_keys, m = (size_t)s.words<lcev::Status>()->n_ops;
   const bool want_wit = aux && aux->witness && aux->witness_kind;
   const bool want_cert = aux && aux->certificate;
   if (aux && (aux->witness || aux->certificate) && !(aux->witness && aux->witness_kind)) {
@@ -165,11 +163,8 @@ int events_check(lc_ctx *c, int64_t n_keys, const lc_opts *opts, lc_key_result *
 }  // namespace
 
 void lcrt::release(EvState &s) {
-  if (s.arena.p) (void)hipFree(s.arena.p);
   if (s.d_res.p) (void)hipFree(s.d_res.p);
-  if (s.h_status) (void)hipHostFree(s.h_status);
-  for (hipEvent_t e : {s.e0, s.e1, s.e2})
-    if (e) (void)hipEventDestroy(e);
+  release(static_cast<SideState &>(s));
 }
 
 extern "C" {

@@ -290,6 +290,23 @@ int lcrt::side_begin(lc_ctx *c, hipStream_t *st) {
   *st = d.stream;
   return 0;
 }
+
+int lcrt::side_begin(lc_ctx *c, SideState &s, int n_events, size_t pinned_bytes, hipStream_t *st) {
+  if (int e = side_begin(c, st)) return e;
+  for (int i = 0; i < n_events; i++)
+    if (!s.ev[i]) HIP_TRY(c, hipEventCreate(&s.ev[i]));
+  if (pinned_bytes && !s.pinned) HIP_TRY(c, hipHostMalloc(&s.pinned, pinned_bytes, 0));
+  return 0;
+}
+
+void lcrt::release(SideState &s) {
+  if (s.arena.p) (void)hipFree(s.arena.p);
+  if (s.pinned) (void)hipHostFree(s.pinned);
+  for (hipEvent_t e : s.ev)
+    if (e) (void)hipEventDestroy(e);
+  s = SideState{};
+}
+
 namespace {
 
 // One request: returns 0 with every key decided or flagged for the later

@@ -9,6 +9,7 @@
 
 #include <functional>
 #include <mutex>
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -132,54 +133,33 @@ struct Dev {
   lc_totals tot{};
 };
 
-// The side checkers' states: one grow-only arena each on the context's first
-// device, carved into the call's arrays (workspace.h); events and pinned words
-// made by the first call; release() frees everything (lc_close).  No device
-// pointer outlives a call but through EvState::w.
+// A side checker's state: one grow-only arena on the context's first device,
+// carved into the call's arrays (workspace.h); events and the pinned words
+// (the checker's own struct) made by its first call (side_begin);
+// release() frees everything (lc_close).  No device pointer outlives a call
+// but through EvState::w.
+constexpr int kSideEvents = 6;
+struct SideState {
+  Buf<char> arena;
+  void *pinned = nullptr;
+  hipEvent_t ev[kSideEvents] = {};
+  template <class T>
+  T *words() const {
+    return static_cast<T *>(pinned);
+  }
+};
 
 // lc_check_events / lc_events_pack.  w: the last events_device call's arrays;
 // events_copy_out and events_check read the packed records through it, so
-// nothing grows the arena in between.
-struct EvState {
-  Buf<char> arena;
-  Buf<lc_key_result> d_res;          // events_check's results
+// nothing grows the arena in between.  The pinned words are an lcev::Status.
+struct EvState : SideState {
+  Buf<lc_key_result> d_res;  // events_check's results
   lcev::Ws w{};
-  lcev::Status *h_status = nullptr;  // pinned
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   lc_events_stats stats{};
 };
 
-struct SfState {  // lc_set_full
-  Buf<char> arena;
-  int64_t *h_small = nullptr;  // pinned: the status words, then the counters
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-};
-
-struct ApState {  // lc_append_check
-  Buf<char> arena;
-  int64_t *h_small = nullptr;  // pinned: the status words, the four counts, then the counters
-  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
-};
-
-struct WrState {  // lc_wr_check
-  Buf<char> arena;
-  int64_t *h_small = nullptr;  // pinned: the status words, the four counts, the rw items' count, the counters
-  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, k0 = nullptr, k1 = nullptr, k2 = nullptr;
-};
-
-struct WtState {  // lc_watch_check
-  Buf<char> arena;
-  // e0 .. e1: the inputs' copies; k0 .. k1: around each run of kernels in turn
-  hipEvent_t e0 = nullptr, e1 = nullptr, k0 = nullptr, k1 = nullptr;
-};
-
+void release(SideState &s);
 void release(EvState &s);
-void release(SfState &s);
-void release(ApState &s);
-void release(WrState &s);
-void release(WtState &s);
 
 void set_err(lc_ctx *c, const std::string &s);
 // key_off[0] >= 0 and key_off monotone over n_keys > 0 keys, or -EINVAL with
@@ -305,6 +285,22 @@ int check_device(lc_ctx *c, const char *who, const void *ops, bool rec32, const 
 // pending status settled, the resident grid gone (it leaves before other
 // work runs).  *st is that device's stream.
 int side_begin(lc_ctx *c, hipStream_t *st);
+// The same for a checker with a state of its own, whose first n_events events
+// and pinned_bytes of pinned words are made where they are missing.
+int side_begin(lc_ctx *c, SideState &s, int n_events, size_t pinned_bytes, hipStream_t *st);
+
+// A side checker's entry point: body(), with the host's std::bad_alloc (its
+// arrays are sized by the caller's arguments) as -ENOMEM and the call's name
+// in the context's error.
+template <class Body>
+int no_bad_alloc(lc_ctx *c, const char *who, Body body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    set_err(c, std::string(who) + ": out of host memory");
+    return -ENOMEM;
+  }
+}
 
 // An input's device copy, which the kernels only read (const in their Ws), as
 // the destination of the host's copy.
@@ -336,8 +332,8 @@ struct lc_ctx {
   std::mutex pin_mu;
   lc_call_profile prof{};  // lc_last_call_profile
   lcrt::EvState evs;       // lc_check_events
-  lcrt::SfState sfs;       // lc_set_full
-  lcrt::ApState aps;       // lc_append_check
-  lcrt::WrState wrs;       // lc_wr_check
-  lcrt::WtState wts;       // lc_watch_check
+  lcrt::SideState sfs;     // lc_set_full
+  lcrt::SideState aps;     // lc_append_check
+  lcrt::SideState wrs;     // lc_wr_check
+  lcrt::SideState wts;     // lc_watch_check
 };

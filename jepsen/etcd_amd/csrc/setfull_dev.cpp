@@ -5,16 +5,25 @@
 // the host's (setfull_host.cpp).
 #include <algorithm>
 #include <chrono>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "runtime.h"
 #include "setfull.h"
+#include "txngraph.h"
 
 using namespace lcrt;
 
 namespace {
+
+// one counter (the phantoms), sharded as the Elle checkers' are (sum_counters)
+static_assert(lcsf::kCounterShards == lctg::kCounterShards && lcsf::kCounterStride == lctg::kCounterStride,
+              "lc_set_full's counter geometry is txngraph.h's");
+constexpr size_t kCountersLen = lcsf::kCounterShards * lcsf::kCounterStride;
+struct Pinned {
+  int32_t status[4];
+  int64_t counters[kCountersLen];
+};
 
 int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_read *reads, int64_t n_reads,
                     const int64_t *read_values, int64_t n_values, int32_t linearizable, lc_sf_element *out,
@@ -34,15 +43,11 @@ int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_s
     if (rc == -EINVAL) set_err(c, "lc_set_full: two adds of one value");
     return rc;
   }
-  SfState &s = c->sfs;
+  SideState &s = c->sfs;
   hipStream_t st;
-  if (int e = side_begin(c, &st)) return e;
-  constexpr size_t kCountersLen = lcsf::kCounterShards * lcsf::kCounterStride;
-  constexpr size_t kSmall = 4 + kCountersLen;  // in int64
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
-  }
+  if (int e = side_begin(c, s, 3, sizeof(Pinned), &st)) return e;
+  const hipEvent_t e0 = s.ev[0], e1 = s.ev[1], e2 = s.ev[2];  // the inputs' copies, then the kernels
+  Pinned &h = *s.words<Pinned>();
   lc_sf_limit_info lim;
   lc_set_full_limits(&lim);
   const size_t ne = (size_t)n_adds, nr = (size_t)n_reads;
@@ -78,7 +83,7 @@ int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_s
   };
   if (int e = ensure(c, s.arena, layout(Carver{}))) return e;
   layout(Carver{s.arena.p});
-  HIP_TRY(c, hipEventRecord(s.e0, st));
+  HIP_TRY(c, hipEventRecord(e0, st));
   HIP_TRY(c, hipMemcpyAsync(writable(w.adds), adds, sizeof(lc_sf_add) * ne, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(writable(w.reads), reads, sizeof(lc_sf_read) * nr, hipMemcpyHostToDevice, st));
   if (n_values)
@@ -86,42 +91,39 @@ int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_s
                               hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(writable(w.work_off), work_off.data(), sizeof(int64_t) * (nr + 1),
                             hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
+  HIP_TRY(c, hipEventRecord(e1, st));
   // no counter or mark of an earlier call survives
   HIP_TRY(c, hipMemsetAsync(w.counters, 0, sizeof(int64_t) * kCountersLen, st));
   HIP_TRY(c, hipMemsetAsync(w.status, 0, sizeof(int32_t) * 4, st));
   HIP_TRY(c, hipMemsetAsync(w.dup_seen, 0, ne, st));
   HIP_TRY(c, lcsf::launch_table(w, st));
-  for (int64_t e0 = 0; e0 < n_adds; e0 += tile_rows)
-    HIP_TRY(c, lcsf::launch_tile(w, e0, std::min(e0 + tile_rows, n_adds), st));
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
-  int64_t *h_counters = s.h_small + 4;
-  HIP_TRY(c, hipMemcpyAsync(h_status, w.status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(h_counters, w.counters, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
+  for (int64_t r0 = 0; r0 < n_adds; r0 += tile_rows)
+    HIP_TRY(c, lcsf::launch_tile(w, r0, std::min(r0 + tile_rows, n_adds), st));
+  HIP_TRY(c, hipEventRecord(e2, st));
+  HIP_TRY(c, hipMemcpyAsync(h.status, w.status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(h.counters, w.counters, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  if (h_status[0]) {
-    set_err(c, "lc_set_full: two adds of one value (element " + std::to_string(h_status[1]) + " is one)");
+  if (h.status[0]) {
+    set_err(c, "lc_set_full: two adds of one value (element " + std::to_string(h.status[1]) + " is one)");
     return -EINVAL;
   }
   HIP_TRY(c, hipMemcpyAsync(out, w.out, sizeof(lc_sf_element) * ne, hipMemcpyDeviceToHost, st));
   std::vector<uint8_t> marked;
-  if (h_status[2]) {
+  if (h.status[2]) {
     marked.resize(ne);
     HIP_TRY(c, hipMemcpyAsync(marked.data(), w.dup_seen, ne, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(c, hipStreamSynchronize(st));
   // duplicates, exact but not fast: the multiplicities of the marked elements
   // in one pass over the payload (a history without duplicates never takes it)
-  if (h_status[2])
+  if (h.status[2])
     if (int rc = lcsf::count_duplicates(adds, n_adds, reads, n_reads, read_values, marked.data(), out)) return rc;
   if (sum) {
     lcsf::summarize(out, n_adds, linearizable, sum);
-    sum->n_phantom = 0;
-    for (int i = 0; i < lcsf::kCounterShards; i++) sum->n_phantom += h_counters[i * lcsf::kCounterStride];
+    sum->n_phantom = lctg::sum_counters(h.counters, 0);
     sum->n_tiles = n_tiles;
-    sum->h2d_ms = elapsed_ms(s.e0, s.e1);
-    sum->kernel_ms = elapsed_ms(s.e1, s.e2);
+    sum->h2d_ms = elapsed_ms(e0, e1);
+    sum->kernel_ms = elapsed_ms(e1, e2);
     sum->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return 0;
@@ -129,21 +131,11 @@ int set_full_device(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_s
 
 }  // namespace
 
-void lcrt::release(SfState &s) {
-  if (s.arena.p) (void)hipFree(s.arena.p);
-  if (s.h_small) (void)hipHostFree(s.h_small);
-  for (hipEvent_t e : {s.e0, s.e1, s.e2})
-    if (e) (void)hipEventDestroy(e);
-}
-
 extern "C" int lc_set_full(lc_ctx *c, const lc_sf_add *adds, int64_t n_adds, const lc_sf_read *reads,
                            int64_t n_reads, const int64_t *read_values, int64_t n_values, int32_t linearizable,
                            lc_sf_element *out, lc_sf_summary *sum) {
   if (!c) return -EINVAL;
-  try {
+  return no_bad_alloc(c, "lc_set_full", [&] {
     return set_full_device(c, adds, n_adds, reads, n_reads, read_values, n_values, linearizable, out, sum);
-  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
-    set_err(c, "lc_set_full: out of host memory");
-    return -ENOMEM;
-  }
+  });
 }

@@ -5,7 +5,6 @@
 // rounds, the canonical log, the batches, the deltas' order and the summary.
 #include <algorithm>
 #include <chrono>
-#include <new>
 #include <string>
 
 #include "runtime.h"
@@ -32,11 +31,11 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
       return -E2BIG;
     }
   const size_t nt = (size_t)n_threads, nv = (size_t)n_values;
-  WtState &s = c->wts;
+  SideState &s = c->wts;
   hipStream_t st;
-  if (int e = side_begin(c, &st)) return e;
-  if (!s.e0)
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.k0, &s.k1}) HIP_TRY(c, hipEventCreate(e));
+  if (int e = side_begin(c, s, 4, 0, &st)) return e;
+  // e0 .. e1: the inputs' copies; k0 .. k1: around each run of kernels in turn
+  const hipEvent_t e0 = s.ev[0], e1 = s.ev[1], k0 = s.ev[2], k1 = s.ev[3];
 
   // The inputs and the threads' tables come first, so that the traces and the
   // edits, whose sizes the compares decide, move nothing when they are carved.
@@ -72,21 +71,21 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
     h_off[t] = threads[t].off;
     h_len[t] = (int32_t)threads[t].len;
   }
-  HIP_TRY(c, hipEventRecord(s.e0, st));
+  HIP_TRY(c, hipEventRecord(e0, st));
   if (nv) HIP_TRY(c, hipMemcpyAsync(d_values, values, sizeof(int64_t) * nv, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_off, h_off.data(), sizeof(int64_t) * nt, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_len, h_len.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipEventRecord(s.e1, st));
+  HIP_TRY(c, hipEventRecord(e1, st));
 
   // the hashes, which propose the classes
   std::vector<lcwt::Hash> hashes(nt);
-  HIP_TRY(c, hipEventRecord(s.k0, st));
+  HIP_TRY(c, hipEventRecord(k0, st));
   HIP_TRY(c, lcwt::launch_hashes(d_values, d_off, d_len, (int)n_threads, d_hash, st));
-  HIP_TRY(c, hipEventRecord(s.k1, st));
+  HIP_TRY(c, hipEventRecord(k1, st));
   HIP_TRY(c, hipMemcpyAsync(hashes.data(), d_hash, sizeof(lcwt::Hash) * nt, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  kernel_ms += elapsed_ms(s.k0, s.k1);
-  const double h2d_ms = elapsed_ms(s.e0, s.e1);
+  kernel_ms += elapsed_ms(k0, k1);
+  const double h2d_ms = elapsed_ms(e0, e1);
 
   // One run of the compare kernel: log b of every pair against log a.
   std::vector<lcwt::Pair> h_pairs;
@@ -98,12 +97,12 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
                                    (int32_t)threads[pr.first].len});
     h_res.resize(h_pairs.size());
     HIP_TRY(c, hipMemcpyAsync(d_pairs, h_pairs.data(), sizeof(lcwt::Pair) * h_pairs.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(s.k0, st));
+    HIP_TRY(c, hipEventRecord(k0, st));
     HIP_TRY(c, lcwt::launch_compare(d_values, d_pairs, (int)h_pairs.size(), d_res, st));
-    HIP_TRY(c, hipEventRecord(s.k1, st));
+    HIP_TRY(c, hipEventRecord(k1, st));
     HIP_TRY(c, hipMemcpyAsync(h_res.data(), d_res, sizeof(lcwt::PairRes) * h_res.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    kernel_ms += elapsed_ms(s.k0, s.k1);
+    kernel_ms += elapsed_ms(k0, k1);
     return 0;
   };
 
@@ -195,12 +194,12 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
   for (size_t bi = 0, i0 = 0; bi < batch_end.size(); i0 = batch_end[bi++]) {
     const size_t nb = batch_end[bi] - i0;
     HIP_TRY(c, hipMemcpyAsync(d_items, h_items.data() + i0, sizeof(lcwt::Item) * nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(s.k0, st));
+    HIP_TRY(c, hipEventRecord(k0, st));
     HIP_TRY(c, lcwt::launch_forward(d_values, d_items, (int)nb, d_trace, d_dist, st));
-    HIP_TRY(c, hipEventRecord(s.k1, st));
+    HIP_TRY(c, hipEventRecord(k1, st));
     HIP_TRY(c, hipMemcpyAsync(h_dist.data() + i0, d_dist, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    kernel_ms += elapsed_ms(s.k0, s.k1);
+    kernel_ms += elapsed_ms(k0, k1);
     for (size_t i = i0; i < i0 + nb; i++) {
       if (h_dist[i] > h_items[i].dcap || h_dist[i] < -1 || h_dist[i] == 0) {
         set_err(c, "lc_watch_check: inconsistent distance");
@@ -209,9 +208,9 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
       if (h_dist[i] > 0) n_edits += h_dist[i];
     }
     if (n_edits > out->edit_cap) continue;  // -ENOSPC below, once every distance is known
-    HIP_TRY(c, hipEventRecord(s.k0, st));
+    HIP_TRY(c, hipEventRecord(k0, st));
     HIP_TRY(c, lcwt::launch_backtrack(d_values, d_items, (int)nb, d_trace, d_dist, d_edits, st));
-    HIP_TRY(c, hipEventRecord(s.k1, st));
+    HIP_TRY(c, hipEventRecord(k1, st));
     for (size_t i = i0; i < i0 + nb; i++) {
       if (h_dist[i] <= 0) continue;
       staged_off[i] = (int64_t)staged.size();
@@ -222,7 +221,7 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
         HIP_TRY(c, hipMemcpyAsync(staged.data() + staged_off[i], d_edits + h_items[i].edit_off,
                                   sizeof(lc_wt_edit) * (size_t)h_dist[i], hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    kernel_ms += elapsed_ms(s.k0, s.k1);
+    kernel_ms += elapsed_ms(k0, k1);
   }
   if (n_edits > out->edit_cap) {
     set_err(c, "lc_watch_check: " + std::to_string(n_edits) + " edits, edit_cap " + std::to_string(out->edit_cap));
@@ -267,20 +266,11 @@ int watch_device(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, cons
 
 }  // namespace
 
-void lcrt::release(WtState &s) {
-  if (s.arena.p) (void)hipFree(s.arena.p);
-  for (hipEvent_t e : {s.e0, s.e1, s.k0, s.k1})
-    if (e) (void)hipEventDestroy(e);
-}
-
 extern "C" int lc_watch_check(lc_ctx *c, const lc_wt_thread *threads, int64_t n_threads, const int64_t *values,
                               int64_t n_values, int64_t n_nonmonotonic, uint32_t flags, const lc_wt_out *out,
                               lc_wt_summary *sum) {
   if (!c) return -EINVAL;
-  try {
+  return no_bad_alloc(c, "lc_watch_check", [&] {
     return watch_device(c, threads, n_threads, values, n_values, n_nonmonotonic, flags, out, sum);
-  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
-    set_err(c, "lc_watch_check: out of host memory");
-    return -ENOMEM;
-  }
+  });
 }

@@ -1,29 +1,23 @@
 // wr.h — what lc_wr_check's host code (wr_host.cpp, g++), its driver
 // (wr_dev.cpp) and its kernels (wr.hip) share.  The rules are
 // include/lincheck_wr.h's.  The (key, value) hash, the table sizing, the
-// sharded counters' geometry, the item chunk, and the edge select / sort /
-// unique and real-time launchers are lc_append_check's (append.h).
+// sharded counters' geometry, the item chunk, and the key-slot, edge select /
+// sort / unique and real-time launchers are txngraph.h's, which
+// lc_append_check shares.
 #pragma once
 #include <stdint.h>
 
 #include <vector>
 
 #include "../../../include/lincheck_wr.h"
-#include "append.h"
+#include "graph_host.h"
+#include "txngraph.h"
 
 namespace lcwr {
 
-using lcap::hash_pair;
-using lcap::kCounterShards;
-using lcap::kCounterStride;
-using lcap::kItemChunk;
-using lcap::kMaxMops;
-using lcap::kMaxPosition;
-using lcap::mix64;
-using lcap::table_capacity;
+using namespace lctg;  // the hash, the limits and the launchers both Elle checkers share
 
 constexpr int64_t kReserved = INT64_MIN;  // no key; as a value, nil
-constexpr int64_t kMaxDeviceMops = int64_t(1) << 29;
 constexpr int64_t kDefaultMaxEdges = int64_t(1) << 27;
 constexpr int kCounters = 5;  // internal, phantom, g1a, g1b, lost-update versions
 
@@ -88,7 +82,8 @@ struct Ws {
 size_t scan_temp_bytes(uint64_t vcap, uint64_t kcap);
 // Tables, the txn pass, rule 6 in `rounds` doublings, the groups and their
 // prefix sums (item_off[vcap] is the number of rw items), the ww slots and the
-// key records.  kslots has kcap entries; *d_n_keys receives the key count.
+// key records.  kslots has kcap entries; *d_n_keys receives the key count;
+// temp has scan_temp_bytes(vcap, kcap).
 hipError_t launch_rules(const Ws &w, int rounds, int32_t *kslots, int64_t *d_n_keys, void *temp, size_t temp_bytes,
                         hipStream_t st);
 // The rw slots: n_items work items into slots[n_mops ..].

@@ -1,6 +1,7 @@
 // wr.hip — the kernels of lc_wr_check (include/lincheck_wr.h): rules 1 to 7
-// over flat arrays.  Rule 8 and the edges' select / sort / unique are
-// lc_append_check's launchers (append.hip); rule 9 is the host's.
+// over flat arrays.  Rule 8, the key table's occupied slots and the edges'
+// select / sort / unique are txngraph.hip's launchers, which lc_append_check
+// calls too; rule 9 is the host's.
 //
 // What the design rests on: in the wfr graph of rule 4 every version has at
 // most one incoming edge (its value has one writer, and a txn gives one edge
@@ -9,10 +10,9 @@
 //
 //  wr_mop_kernel (a thread per mop): the mop's key into the key table and its
 //    (key, value) into the version table — written and read values alike, nil
-//    once it is read — as ap_mop_kernel does: one 64-bit compare-and-swap per
-//    insertion, the hash's tag in the high word and a mop that names the pair
-//    in the low one, linear probing.  A write claims the entry's writer word; a
-//    second claim raises status[0].  Also rule 1's "last write".
+//    once it is read — the two table formats of txngraph_dev.h.  A write
+//    claims the entry's writer word; a second claim raises status[0].  Also
+//    rule 1's "last write".
 //  wr_txn_kernel (a thread per txn): rules 2, 3 and 5, the wr slots, the
 //    per-version reader counts, each wfr edge as its head's parent pointer, a
 //    self-loop marking its key at once.  Counts: per wave, onto counters 128 B
@@ -36,80 +36,30 @@
 // Every loop is bounded by a txn, mop, version, edge, round or table count; no
 // workgroup waits for another; results leave through vector stores.
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
 
+#include "txngraph_dev.h"
 #include "wr.h"
 
 namespace lcwr {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxGrid = 256 * 8;
-constexpr unsigned long long kEmptyWord = ~0ull;
-constexpr int64_t kKeyXor = 0x7FFFFFFFFFFFFFFFll;  // a stored key is key ^ this: the reserved key reads ~0
-constexpr unsigned long long kSign = 1ull << 63;    // value ^ this: unsigned order is the int64 order
-
-int grid_for(int64_t items, int64_t per_block) {
-  int64_t g = (items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g < kMaxGrid ? g : kMaxGrid);
-}
-
-__device__ __forceinline__ bool names_pair(const Ws &w, unsigned long long word, uint64_t h, int64_t key,
-                                           int64_t value) {
-  if ((word >> 32) != (h >> 32)) return false;
-  const lc_wr_mop &o = w.mops[(uint32_t)word];
-  return o.key == key && o.value == value;
-}
-
-// The slot of (key, value) in the version table, or -1.
-__device__ __forceinline__ int32_t find_version(const Ws &w, int64_t key, int64_t value) {
-  const uint64_t h = hash_pair(key, value);
-  uint64_t s = h & (w.vcap - 1);
-  for (uint64_t p = 0; p < w.vcap; p++) {
-    const unsigned long long word = w.vtab[s];
-    if (word == kEmptyWord) return -1;
-    if (names_pair(w, word, h, key, value)) return (int32_t)s;
-    s = (s + 1) & (w.vcap - 1);
-  }
-  return -1;
-}
+constexpr unsigned long long kSign = 1ull << 63;  // value ^ this: unsigned order is the int64 order
 
 __global__ __launch_bounds__(kThreads) void wr_mop_kernel(Ws w) {
   unsigned long long *ktab = reinterpret_cast<unsigned long long *>(w.ktab);
   for (int64_t m = blockIdx.x * (int64_t)kThreads + threadIdx.x; m < w.n_mops; m += (int64_t)gridDim.x * kThreads) {
     const lc_wr_mop o = w.mops[m];
-    const unsigned long long enc = (unsigned long long)(o.key ^ kKeyXor);
-    uint64_t ks = mix64((uint64_t)o.key) & (w.kcap - 1);
-    for (uint64_t p = 0; p < w.kcap; p++) {
-      const unsigned long long old = atomicCAS(&ktab[ks], kEmptyWord, enc);
-      if (old == kEmptyWord || old == enc) break;
-      ks = (ks + 1) & (w.kcap - 1);
-    }
-    w.mop_kslot[m] = (int32_t)ks;
+    const int32_t ks = key_claim(ktab, w.kcap, o.key);
+    w.mop_kslot[m] = ks;
     int32_t vs = -1;
     if (o.f == LC_WR_WRITE || o.known) {
-      const uint64_t h = hash_pair(o.key, o.value);
-      const unsigned long long word = ((h >> 32) << 32) | (unsigned long long)(uint32_t)m;
-      uint64_t s = h & (w.vcap - 1);
-      for (uint64_t p = 0; p < w.vcap; p++) {
-        const unsigned long long old = atomicCAS(&w.vtab[s], kEmptyWord, word);
-        if (old == kEmptyWord) {  // a new version; nil is counted by the key record itself
-          if (o.value != kReserved) atomicAdd(&w.kcount[3 * (int64_t)ks + 1], 1);
-          vs = (int32_t)s;
-          break;
-        }
-        if (names_pair(w, old, h, o.key, o.value)) {
-          vs = (int32_t)s;
-          break;
-        }
-        s = (s + 1) & (w.vcap - 1);
-      }
+      bool inserted;
+      vs = pair_claim(w.vtab, w.vcap, w.mops, m, o.key, o.value, &inserted);
+      // a new version; nil is counted by the key record itself
+      if (inserted && o.value != kReserved) atomicAdd(&w.kcount[3 * (int64_t)ks + 1], 1);
     }
     w.mop_vslot[m] = vs;
     if (o.f != LC_WR_WRITE || vs < 0) continue;
@@ -130,7 +80,6 @@ __global__ __launch_bounds__(kThreads) void wr_mop_kernel(Ws w) {
 }
 
 __global__ __launch_bounds__(kThreads) void wr_txn_kernel(Ws w) {
-  __shared__ long long s_cnt[kWaves][kCounters];
   long long cnt[kCounters] = {0, 0, 0, 0, 0};
   for (int64_t t = blockIdx.x * (int64_t)kThreads + threadIdx.x; t < w.n_txns; t += (int64_t)gridDim.x * kThreads) {
     const lc_wr_txn x = w.txns[t];
@@ -190,20 +139,7 @@ __global__ __launch_bounds__(kThreads) void wr_txn_kernel(Ws w) {
     }
     w.txn_flags[t] = tf;
   }
-  for (int b = 0; b < kCounters; b++) {
-    long long v = cnt[b];
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6][b] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kCounters) {
-    long long v = 0;
-    for (int i = 0; i < kWaves; i++) v += s_cnt[i][threadIdx.x];
-    if (v)
-      atomicAdd(reinterpret_cast<unsigned long long *>(
-                    &w.counters[((int64_t)threadIdx.x * kCounterShards + blockIdx.x % kCounterShards) * kCounterStride]),
-                (unsigned long long)v);
-  }
+  flush_counters(cnt, w.counters);
 }
 
 __global__ __launch_bounds__(kThreads) void wr_jump_kernel(Ws w, const int32_t *__restrict__ in,
@@ -231,7 +167,7 @@ __global__ __launch_bounds__(kThreads) void wr_mark_kernel(Ws w, const int32_t *
       }
     }
     if (w.txns[w.mop_txn[m]].type == LC_WR_FAIL) continue;
-    const int32_t ns = find_version(w, o.key, kReserved);
+    const int32_t ns = pair_find(w.vtab, w.vcap, w.mops, o.key, kReserved);
     w.mop_nil[m] = ns;
     if (ns >= 0) atomicAdd(&w.vnchild[ns], 1);
   }
@@ -323,21 +259,15 @@ __global__ __launch_bounds__(kThreads) void wr_keys_kernel(Ws w, const int32_t *
   }
 }
 
-struct KeySet {
-  const int64_t *ktab;
-  __host__ __device__ bool operator()(int32_t s) const { return ktab[s] != -1; }
-};
-
 }  // namespace
 
 size_t scan_temp_bytes(uint64_t vcap, uint64_t kcap) {
-  size_t a = 0, b = 0, c = 0;
+  size_t a = 0, b = 0;
   int32_t *p = nullptr;
   int64_t *q = nullptr;
   (void)rocprim::exclusive_scan(nullptr, a, p, p, int32_t(0), (size_t)vcap, rocprim::plus<int32_t>());
   (void)rocprim::exclusive_scan(nullptr, b, q, q, int64_t(0), (size_t)vcap + 1, rocprim::plus<int64_t>());
-  (void)rocprim::select(nullptr, c, rocprim::counting_iterator<int32_t>(0), p, q, (size_t)kcap, KeySet{nullptr});
-  return std::max(a, std::max(b, c));
+  return std::max(a, std::max(b, key_temp_bytes(kcap)));
 }
 
 hipError_t launch_rules(const Ws &w, int rounds, int32_t *kslots, int64_t *d_n_keys, void *temp, size_t temp_bytes,
@@ -367,9 +297,7 @@ hipError_t launch_rules(const Ws &w, int rounds, int32_t *kslots, int64_t *d_n_k
                               st);
   if (e != hipSuccess) return e;
   wr_fill_kernel<<<g_mops, kThreads, 0, st>>>(w);
-  bytes = temp_bytes;
-  e = rocprim::select(temp, bytes, rocprim::counting_iterator<int32_t>(0), kslots, d_n_keys, (size_t)w.kcap,
-                      KeySet{w.ktab}, st);
+  e = launch_key_slots(w.ktab, w.kcap, kslots, d_n_keys, temp, temp_bytes, st);
   if (e != hipSuccess) return e;
   wr_keys_kernel<<<g_mops, kThreads, 0, st>>>(w, kslots, d_n_keys);
   return hipGetLastError();

@@ -1,10 +1,9 @@
 // wr_dev.cpp — lc_wr_check's driver (include/lincheck_wr.h): the arrays
 // copied to the context's first device; rules 1 to 8 there (wr.hip, and
-// append.hip's launchers for the edges and real time); rule 9 and the summary
+// txngraph.hip's launchers for the edges and real time); rule 9 and the summary
 // on the host (wr_host.cpp, graph_host.cpp).
 #include <algorithm>
 #include <chrono>
-#include <new>
 #include <string>
 
 #include "runtime.h"
@@ -13,6 +12,14 @@
 using namespace lcrt;
 
 namespace {
+
+constexpr size_t kCountersLen = lcwr::kCounters * lcwr::kCounterShards * lcwr::kCounterStride;
+struct Pinned {
+  int32_t status[4];
+  int64_t count[4];  // edges selected, unique edges, OK txns, keys
+  int64_t items;     // the rw items
+  int64_t counters[kCountersLen];
+};
 
 int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_t n_mops,
               uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum) {
@@ -31,21 +38,18 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
     return -E2BIG;
   }
   const size_t nt = (size_t)n_txns, nm = (size_t)n_mops;
-  WrState &s = c->wrs;
+  SideState &s = c->wrs;
   hipStream_t st;
-  if (int e = side_begin(c, &st)) return e;
-  constexpr size_t kCountersLen = lcwr::kCounters * lcwr::kCounterShards * lcwr::kCounterStride;
-  constexpr size_t kSmall = 7 + kCountersLen;  // in int64: 4 status words, 4 counts, the rw items, the counters
-  if (!s.e0) {
-    for (hipEvent_t *e : {&s.e0, &s.e1, &s.e2, &s.k0, &s.k1, &s.k2}) HIP_TRY(c, hipEventCreate(e));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&s.h_small), sizeof(int64_t) * kSmall, 0));
-  }
+  if (int e = side_begin(c, s, 6, sizeof(Pinned), &st)) return e;
+  // e0 .. e1: the inputs' copies; k0 .. k1 and k2 .. e2: the kernels' two runs
+  const hipEvent_t e0 = s.ev[0], e1 = s.ev[1], e2 = s.ev[2], k0 = s.ev[3], k1 = s.ev[4], k2 = s.ev[5];
+  Pinned &h = *s.words<Pinned>();
   // both tables: entries are at most one per mop
   const uint64_t vcap = lcwr::table_capacity(n_mops), kcap = vcap;
   int rounds = 1;  // rule 6: 2^rounds above the versions' number (at most one per mop)
   while (rounds < 32 && (int64_t(1) << rounds) <= n_mops) rounds++;
   rounds++;
-  const size_t temp_bytes = std::max(lcwr::scan_temp_bytes(vcap, kcap), lcap::rt_temp_bytes(n_txns));
+  const size_t temp_bytes = std::max(lcwr::scan_temp_bytes(vcap, kcap), lcwr::rt_temp_bytes(n_txns));
   lcwr::Ws w{};
   w.n_txns = n_txns;
   w.n_mops = n_mops;
@@ -56,7 +60,8 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
   // unique edges, OK txns, keys), real time's arrays, rocprim's temporary
   // storage; then, sized by the rw items, the two edge buffers and theirs
   lc_wr_edge *d_edges_b = nullptr;
-  int32_t *d_kslots = nullptr, *rt = nullptr;
+  int32_t *d_kslots = nullptr;
+  lcwr::RtArrays rt{};
   int64_t *d_count = nullptr;
   uint8_t *d_temp = nullptr, *d_etemp = nullptr;
   // Everything the rules need comes first, so that the edge buffers, whose
@@ -96,31 +101,27 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
     w.counters = ws.take<int64_t>(kCountersLen);
     d_count = ws.take<int64_t>(4);
     w.status = ws.take<int32_t>(4);
-    rt = ws.take<int32_t>(7 * nt);  // ok_idx, ok_comp, byc, comp_sorted, pm, rt_lo, rt_hi: n_txns each
+    rt.carve(ws, nt);
     d_temp = ws.take<uint8_t>(temp_bytes);
     const size_t n_slots = nm + (size_t)n_items;
     w.slots = ws.take<lc_wr_edge>(n_slots);
     d_edges_b = ws.take<lc_wr_edge>(n_slots);
-    d_etemp = ws.take<uint8_t>(lcap::edge_temp_bytes((int64_t)n_slots));
+    d_etemp = ws.take<uint8_t>(lcwr::edge_temp_bytes((int64_t)n_slots));
     return ws.size;
   };
-  int32_t *h_status = reinterpret_cast<int32_t *>(s.h_small);
-  int64_t *h_count = s.h_small + 2, *h_items = s.h_small + 6, *h_counters = s.h_small + 7;
-  // (counts: edges selected, unique edges, OK txns, keys)
-  int32_t *d_byc = nullptr, *d_lo = nullptr, *d_hi = nullptr;
   // The copies in and everything up to the synchronisation that brings the
   // status and the number of rw items, with room for `room` of them.
   auto first_run = [&](int64_t room) -> int {
     if (int e = ensure(c, s.arena, layout(Carver{}, room))) return e;
     layout(Carver{s.arena.p}, room);
-    HIP_TRY(c, hipEventRecord(s.e0, st));
+    HIP_TRY(c, hipEventRecord(e0, st));
     HIP_TRY(c, hipMemcpyAsync(writable(w.txns), txns, sizeof(lc_wr_txn) * nt, hipMemcpyHostToDevice, st));
     if (nm) {
       HIP_TRY(c, hipMemcpyAsync(writable(w.mops), mops, sizeof(lc_wr_mop) * nm, hipMemcpyHostToDevice, st));
       HIP_TRY(c, hipMemcpyAsync(writable(w.mop_txn), p.mop_txn.data(), sizeof(int32_t) * nm, hipMemcpyHostToDevice,
                                 st));
     }
-    HIP_TRY(c, hipEventRecord(s.e1, st));
+    HIP_TRY(c, hipEventRecord(e1, st));
     // nothing of an earlier call survives: empty tables (every empty word is
     // all ones), no writers, parents or pointers (-1), no counts, no flags
     HIP_TRY(c, hipMemsetAsync(w.vtab, 0xFF, sizeof(unsigned long long) * vcap, st));
@@ -149,30 +150,25 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
     HIP_TRY(c, hipMemsetAsync(w.counters, 0, sizeof(int64_t) * kCountersLen, st));
     HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(int64_t) * 4, st));
     HIP_TRY(c, hipMemsetAsync(w.status, 0, sizeof(int32_t) * 4, st));
-    d_byc = rt + 2 * nt, d_lo = rt + 5 * nt, d_hi = rt + 6 * nt;
-    HIP_TRY(c, hipEventRecord(s.k0, st));
+    HIP_TRY(c, hipEventRecord(k0, st));
     if (nm) HIP_TRY(c, lcwr::launch_rules(w, rounds, d_kslots, d_count + 3, d_temp, temp_bytes, st));
-    lcap::Ws rw{};  // (launch_real_time reads the txns alone)
-    rw.txns = w.txns;
-    rw.n_txns = n_txns;
-    HIP_TRY(c, lcap::launch_real_time(rw, p.n_ok, rt, rt + nt, d_byc, rt + 3 * nt, rt + 4 * nt, d_lo, d_hi,
-                                      d_count + 2, d_temp, temp_bytes, st));
-    HIP_TRY(c, hipEventRecord(s.k1, st));
-    HIP_TRY(c, hipMemcpyAsync(h_status, w.status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_count, d_count, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_items, w.item_off + vcap, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(h_counters, w.counters, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, lcwr::launch_real_time(w.txns, n_txns, p.n_ok, rt, d_count + 2, d_temp, temp_bytes, st));
+    HIP_TRY(c, hipEventRecord(k1, st));
+    HIP_TRY(c, hipMemcpyAsync(h.status, w.status, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h.count, d_count, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&h.items, w.item_off + vcap, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(h.counters, w.counters, sizeof(int64_t) * kCountersLen, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     return 0;
   };
   // the first run guesses one rw item per mop (the arena keeps what earlier calls needed)
   int64_t room = std::min<int64_t>(n_mops, std::max<int64_t>(lim.max_edges - n_mops, 0));
   if (int e = first_run(room)) return e;
-  if (h_status[0]) {
-    set_err(c, "lc_wr_check: two writes of one (key, value) (mop " + std::to_string(h_status[1]) + " is one)");
+  if (h.status[0]) {
+    set_err(c, "lc_wr_check: two writes of one (key, value) (mop " + std::to_string(h.status[1]) + " is one)");
     return -EINVAL;
   }
-  const int64_t n_items = h_items[0], n_keys = h_count[3];
+  const int64_t n_items = h.items, n_keys = h.count[3];
   if (n_items < 0 || n_keys > n_mops) {
     set_err(c, "lc_wr_check: inconsistent item or key count");
     return -EIO;
@@ -190,38 +186,35 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
       layout(Carver{s.arena.p}, n_items);
     } else {
       if (int e = first_run(n_items)) return e;
-      if (h_status[0] || h_items[0] != n_items) {
+      if (h.status[0] || h.items != n_items) {
         set_err(c, "lc_wr_check: the second run disagrees with the first");
         return -EIO;
       }
     }
   }
   const size_t n_slots = nm + (size_t)n_items;
-  const size_t etemp_bytes = lcap::edge_temp_bytes((int64_t)n_slots);
-  h_count[1] = 0;
-  HIP_TRY(c, hipEventRecord(s.k2, st));
+  const size_t etemp_bytes = lcwr::edge_temp_bytes((int64_t)n_slots);
+  h.count[1] = 0;
+  HIP_TRY(c, hipEventRecord(k2, st));
   if (n_items) HIP_TRY(c, hipMemsetAsync(w.slots + nm, 0xFF, sizeof(lc_wr_edge) * (size_t)n_items, st));
   HIP_TRY(c, lcwr::launch_items(w, n_items, st));
   int64_t n_sel = 0;
   if (n_slots) {
-    lcap::Ws ew{};  // (launch_edge_select reads the slots and their number alone)
-    ew.slots = w.slots;
-    ew.n_work = (int64_t)n_slots;
-    HIP_TRY(c, lcap::launch_edge_select(ew, d_edges_b, d_count, d_etemp, etemp_bytes, st));
-    HIP_TRY(c, hipMemcpyAsync(h_count, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, lcwr::launch_edge_select(w.slots, (int64_t)n_slots, d_edges_b, d_count, d_etemp, etemp_bytes, st));
+    HIP_TRY(c, hipMemcpyAsync(h.count, d_count, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    n_sel = h_count[0];
+    n_sel = h.count[0];
     if (n_sel < 0 || n_sel > (int64_t)n_slots) {
       set_err(c, "lc_wr_check: inconsistent edge count");
       return -EIO;
     }
     // sorted into the slots' place, unique back into the other buffer
-    if (n_sel > 0) HIP_TRY(c, lcap::launch_edge_sort(d_edges_b, w.slots, n_sel, d_count + 1, d_etemp, etemp_bytes, st));
+    if (n_sel > 0) HIP_TRY(c, lcwr::launch_edge_sort(d_edges_b, w.slots, n_sel, d_count + 1, d_etemp, etemp_bytes, st));
   }
-  HIP_TRY(c, hipEventRecord(s.e2, st));
-  if (n_sel > 0) HIP_TRY(c, hipMemcpyAsync(h_count + 1, d_count + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipEventRecord(e2, st));
+  if (n_sel > 0) HIP_TRY(c, hipMemcpyAsync(h.count + 1, d_count + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  const int64_t n_edges = h_count[1];
+  const int64_t n_edges = h.count[1];
   if (n_edges < 0 || n_edges > n_sel) {
     set_err(c, "lc_wr_check: inconsistent unique edge count");
     return -EIO;
@@ -239,23 +232,21 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
   HIP_TRY(c, hipMemcpyAsync(out->txn_flags, w.txn_flags, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
   if (n_keys)
     HIP_TRY(c, hipMemcpyAsync(out->keys, w.keys, sizeof(lc_wr_key) * (size_t)n_keys, hipMemcpyDeviceToHost, st));
-  if (p.n_ok) HIP_TRY(c, hipMemcpyAsync(out->byc, d_byc, sizeof(int32_t) * (size_t)p.n_ok, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->rt_lo, d_lo, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(out->rt_hi, d_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  if (p.n_ok) HIP_TRY(c, hipMemcpyAsync(out->byc, rt.byc, sizeof(int32_t) * (size_t)p.n_ok, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->rt_lo, rt.rt_lo, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(out->rt_hi, rt.rt_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
   if (n_edges > 0)  // only the unique edges reach the caller
     HIP_TRY(c, hipMemcpyAsync(out->edges, d_edges_b, sizeof(lc_wr_edge) * (size_t)n_edges, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   std::sort(out->keys, out->keys + n_keys, [](const lc_wr_key &a, const lc_wr_key &b) { return a.key < b.key; });
-  int64_t counts[lcwr::kCounters] = {0};
-  for (int b = 0; b < lcwr::kCounters; b++)
-    for (int i = 0; i < lcwr::kCounterShards; i++)
-      counts[b] += h_counters[((size_t)b * lcwr::kCounterShards + i) * lcwr::kCounterStride];
+  int64_t counts[lcwr::kCounters];
+  for (int b = 0; b < lcwr::kCounters; b++) counts[b] = lcwr::sum_counters(h.counters, b);
   lc_wr_summary sm;
   lcwr::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, counts, &sm);
   sm.n_edges_raw = n_sel;
-  sm.h2d_ms = elapsed_ms(s.e0, s.e1);
-  sm.kernel_ms = elapsed_ms(s.k0, s.k1);
-  sm.kernel_ms += elapsed_ms(s.k2, s.e2);
+  sm.h2d_ms = elapsed_ms(e0, e1);
+  sm.kernel_ms = elapsed_ms(k0, k1);
+  sm.kernel_ms += elapsed_ms(k2, e2);
   sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = sm;
   return 0;
@@ -263,20 +254,8 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
 
 }  // namespace
 
-void lcrt::release(WrState &s) {
-  if (s.arena.p) (void)hipFree(s.arena.p);
-  if (s.h_small) (void)hipHostFree(s.h_small);
-  for (hipEvent_t e : {s.e0, s.e1, s.e2, s.k0, s.k1, s.k2})
-    if (e) (void)hipEventDestroy(e);
-}
-
 extern "C" int lc_wr_check(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_t n_mops,
                            uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum) {
   if (!c) return -EINVAL;
-  try {
-    return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum);
-  } catch (const std::bad_alloc &) {  // (the host's arrays: sized by the caller's arguments)
-    set_err(c, "lc_wr_check: out of host memory");
-    return -ENOMEM;
-  }
+  return no_bad_alloc(c, "lc_wr_check", [&] { return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum); });
 }

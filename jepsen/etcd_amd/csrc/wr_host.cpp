@@ -15,25 +15,6 @@
 
 namespace lcwr {
 
-namespace {
-
-struct PairHash {
-  size_t operator()(const std::pair<int64_t, int64_t> &p) const { return (size_t)hash_pair(p.first, p.second); }
-};
-
-bool edge_less(const lc_wr_edge &a, const lc_wr_edge &b) {
-  if (a.from != b.from) return a.from < b.from;
-  if (a.to != b.to) return a.to < b.to;
-  if (a.type != b.type) return a.type < b.type;
-  return a.key < b.key;
-}
-
-bool edge_same(const lc_wr_edge &a, const lc_wr_edge &b) {
-  return a.from == b.from && a.to == b.to && a.type == b.type && a.key == b.key;
-}
-
-}  // namespace
-
 int prepare(const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_t n_mops, uint32_t flags,
             const lc_wr_out *out, Prep *p, const char **err) {
 #define LCWR_BAD(text) \
@@ -45,25 +26,14 @@ int prepare(const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_
     LCWR_BAD("null array or negative count");
   if (flags & ~LC_WR_WFR_KEYS) LCWR_BAD("unknown flag");
   if (n_mops >= kMaxMops || n_txns >= kMaxMops) LCWR_BAD("2^31 - 1 or more txns or mops");
-  if (!out || !out->mop_flags || !out->txn_flags || !out->keys || !out->edges || !out->byc || !out->rt_lo ||
-      !out->rt_hi || !out->scc || !out->scc_class || !out->steps || !out->cycle_off || !out->cycle_scc)
-    LCWR_BAD("null out");
+  if (null_out(out)) LCWR_BAD("null out");
   if (out->edge_cap < 0) LCWR_BAD("negative edge_cap");
   p->mop_txn.resize((size_t)n_mops);
   int64_t next = 0, prev_inv = -1;
   for (int64_t t = 0; t < n_txns; t++) {
     const lc_wr_txn &x = txns[t];
-    if (x.inv_pos <= prev_inv || x.inv_pos >= kMaxPosition) LCWR_BAD("txns not strictly ascending by inv_pos");
+    if (const char *bad = check_txn(x, prev_inv, next, n_mops)) LCWR_BAD(bad);
     prev_inv = x.inv_pos;
-    if (x.type == LC_WR_INFO) {
-      if (x.comp_pos != -1) LCWR_BAD("an INFO txn with a comp_pos");
-    } else if (x.type == LC_WR_OK || x.type == LC_WR_FAIL) {
-      if (x.comp_pos <= x.inv_pos || x.comp_pos >= kMaxPosition) LCWR_BAD("comp_pos not above inv_pos");
-    } else {
-      LCWR_BAD("unknown txn type");
-    }
-    if (x.mop_off != next || x.mop_len < 0 || x.mop_len > n_mops - next)
-      LCWR_BAD("the txns' mop ranges do not tile the mops in order");
     for (int64_t m = next; m < next + x.mop_len; m++) {
       const lc_wr_mop &o = mops[m];
       p->mop_txn[(size_t)m] = (int32_t)t;

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 COUNTS = ("valid", "n_incompatible_order", "n_nonprefix", "n_duplicate", "n_g1a", "n_phantom", "n_g1b",
           "n_internal", "n_class", "n_keys", "n_ok", "n_nodes", "n_edges", "n_scc", "n_cycles_returned")
-ITEM_CHUNK = 4096  # append.h, kItemChunk
+ITEM_CHUNK = 4096  # txngraph.h, kItemChunk
 M64 = (1 << 64) - 1
 I64_MAX, I64_LOW = 2 ** 63 - 1, -2 ** 63 + 1
 
@@ -80,7 +80,7 @@ def _mix64(x):
 
 
 def _hash_pair(key, element):
-    """append.h's hash_pair."""
+    """txngraph.h's hash_pair."""
     return _mix64(_mix64(key) + 0x9E3779B97F4A7C15 + (element & M64))
 
 

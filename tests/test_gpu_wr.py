@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 COUNTS = ("valid", "n_internal", "n_phantom", "n_g1a", "n_g1b", "n_cyclic_keys", "n_lost_update", "n_class",
           "n_keys", "n_versions", "n_ok", "n_nodes", "n_edges", "n_edges_raw", "n_scc", "n_cycles_returned")
-ITEM_CHUNK = 4096  # append.h, kItemChunk
+ITEM_CHUNK = 4096  # txngraph.h, kItemChunk
 M64 = (1 << 64) - 1
 I64_MAX, I64_LOW = 2 ** 63 - 1, -2 ** 63 + 1
 NIL = abi.LC_WR_NIL
@@ -89,7 +89,7 @@ def _mix64(x):
 
 
 def _hash_pair(key, value):
-    """append.h's hash_pair."""
+    """txngraph.h's hash_pair."""
     return _mix64(_mix64(key) + 0x9E3779B97F4A7C15 + (value & M64))
 
 
