@@ -579,5 +579,7 @@ const char *lc_build_id(void);
 #include "lincheck_wr.h"
 /* lc_watch_check: the :watch workload's log-convergence checker on the device */
 #include "lincheck_watch.h"
+/* lc_perf_stats: the composed checker's :stats and :perf keys on the device */
+#include "lincheck_perf.h"
 
 #endif /* LINCHECK_H */

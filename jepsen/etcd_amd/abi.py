@@ -313,6 +313,43 @@ class LcWtLimits(ctypes.Structure):
                 ("max_device_len", ctypes.c_int64), ("hash_mask", ctypes.c_uint64)]
 
 
+# lc_perf_stats (include/lincheck_perf.h)
+LC_PS_MAX_Q = 8
+LC_PS_NONE = -2 ** 63
+PS_EVENT_DTYPE = np.dtype([("time", "<i8"), ("process", "<i4"), ("f", "<u2"), ("type", "u1"), ("pad", "u1")])
+assert PS_EVENT_DTYPE.itemsize == 16
+PS_DEFAULT_QS = (0.5, 0.95, 0.99, 1.0)
+PS_DEFAULT_RATE_DT_NS = 10 * 10 ** 9
+PS_DEFAULT_QUANT_DT_NS = 30 * 10 ** 9
+
+
+class LcPsParams(ctypes.Structure):
+    _fields_ = [("n_f", ctypes.c_int32), ("n_q", ctypes.c_int32), ("q", ctypes.c_double * LC_PS_MAX_Q),
+                ("rate_dt_ns", ctypes.c_int64), ("quant_dt_ns", ctypes.c_int64)]
+
+
+class LcPsOut(ctypes.Structure):
+    _fields_ = [("by_f", ctypes.c_void_p), ("comp_pos", ctypes.c_void_p), ("latency_ns", ctypes.c_void_p),
+                ("rate", ctypes.c_void_p), ("rate_cap", ctypes.c_int64), ("quant", ctypes.c_void_p),
+                ("quant_n", ctypes.c_void_p), ("quant_cap", ctypes.c_int64)]
+
+
+class LcPsSummary(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int32), ("pad", ctypes.c_int32), ("n_events", ctypes.c_int64),
+                ("n_client", ctypes.c_int64), ("n_pairs", ctypes.c_int64), ("n_pending", ctypes.c_int64),
+                ("n_ignored_completions", ctypes.c_int64), ("n_mismatched_f", ctypes.c_int64),
+                ("count", ctypes.c_int64), ("ok", ctypes.c_int64), ("fail", ctypes.c_int64),
+                ("info", ctypes.c_int64), ("t_max", ctypes.c_int64), ("n_rate_buckets", ctypes.c_int64),
+                ("n_quant_buckets", ctypes.c_int64), ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
+
+
+class LcPsLimits(ctypes.Structure):
+    _fields_ = [("max_f", ctypes.c_int64), ("max_table_entries", ctypes.c_int64), ("lds_entries", ctypes.c_int64),
+                ("default_lds_entries", ctypes.c_int64), ("wave", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("chunk", ctypes.c_int32), ("max_grid", ctypes.c_int32)]
+
+
 class LcSynthParams(ctypes.Structure):
     _fields_ = [("n_keys", ctypes.c_int64), ("ops_per_key", ctypes.c_int64),
                 ("concurrency", ctypes.c_int32), ("n_values", ctypes.c_int32),
@@ -467,6 +504,14 @@ def lib():
             L.lc_watch_check.restype = ctypes.c_int
             L.lc_watch_limits.argtypes = [ctypes.POINTER(LcWtLimits)]
             L.lc_watch_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_perf_stats"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            ps = [p, i64, ctypes.POINTER(LcPsParams), ctypes.POINTER(LcPsOut), ctypes.POINTER(LcPsSummary)]
+            L.lc_perf_stats_host.argtypes = ps
+            L.lc_perf_stats_host.restype = ctypes.c_int
+            L.lc_perf_stats.argtypes = [vp] + ps
+            L.lc_perf_stats.restype = ctypes.c_int
+            L.lc_perf_stats_limits.argtypes = [ctypes.POINTER(LcPsLimits)]
+            L.lc_perf_stats_limits.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -814,6 +859,81 @@ def watch_limits():
     return {f: getattr(s, f) for f, _ in LcWtLimits._fields_}
 
 
+class _PerfStatsCall:
+    """One lc_perf_stats(_host) call's arrays: the events made contiguous, the
+    tables allocated with rate_cap / quant_cap buckets per row (None: rule 7's
+    counts, from the client events' largest time), the point arrays on
+    request."""
+
+    def __init__(self, events, n_f, qs, rate_dt_ns, quant_dt_ns, points, rate_cap, quant_cap):
+        self.events = np.ascontiguousarray(events, dtype=PS_EVENT_DTYPE)
+        qs = [float(q) for q in qs]
+        self.params = LcPsParams(n_f=int(n_f), n_q=len(qs), rate_dt_ns=int(rate_dt_ns), quant_dt_ns=int(quant_dt_ns))
+        for i, q in enumerate(qs[:LC_PS_MAX_Q]):
+            self.params.q[i] = q
+        n, nf, nq = len(self.events), max(int(n_f), 1), min(len(qs), LC_PS_MAX_Q)
+        client = self.events["time"][self.events["process"] >= 0]
+        t_max = max(int(client.max()), 0) if len(client) else 0
+        if rate_cap is None:
+            rate_cap = t_max // int(rate_dt_ns) + 1 if rate_dt_ns > 0 else 1
+        if quant_cap is None:
+            quant_cap = t_max // int(quant_dt_ns) + 1 if quant_dt_ns > 0 else 1
+        self.rate_cap, self.quant_cap = int(rate_cap), int(quant_cap)
+        if max(nf * 3 * self.rate_cap, nf * self.quant_cap * max(nq, 1)) > 1 << 28:  # (the library answers -E2BIG)
+            self.rate_cap = self.quant_cap = 1
+        self.arrays = {"by_f": np.zeros((nf, 4), dtype=np.int64),
+                       "rate": np.zeros((nf, 3, max(self.rate_cap, 0)), dtype=np.int64),
+                       "quant": np.zeros((nf, max(self.quant_cap, 0), nq), dtype=np.int64),
+                       "quant_n": np.zeros((nf, max(self.quant_cap, 0)), dtype=np.int64),
+                       "comp_pos": np.zeros(n, dtype=np.int32) if points else None,
+                       "latency_ns": np.zeros(n, dtype=np.int64) if points else None}
+        # (a pointer that is never NULL for the tables: an empty array's may be)
+        self._room = {k: (v if v is None or v.size else np.zeros(1, dtype=v.dtype)) for k, v in self.arrays.items()}
+        self.out = LcPsOut(rate_cap=self.rate_cap, quant_cap=self.quant_cap,
+                           **{k: _ptr(v) for k, v in self._room.items()})
+        self.summary = LcPsSummary()
+
+    def args(self):
+        return (_ptr(self.events) if len(self.events) else None, len(self.events), ctypes.byref(self.params),
+                ctypes.byref(self.out), ctypes.byref(self.summary))
+
+    def result(self):
+        return self.arrays, {f: getattr(self.summary, f) for f, _ in LcPsSummary._fields_ if f != "pad"}
+
+
+def _perf_stats_run(fn, error_text, events, n_f, qs, rate_dt_ns, quant_dt_ns, points, rate_cap, quant_cap):
+    call = _PerfStatsCall(events, n_f, qs, rate_dt_ns, quant_dt_ns, points, rate_cap, quant_cap)
+    rc = fn(call)
+    if rc != 0:
+        err = LcError(rc, error_text())
+        # -ENOSPC: rule 7's counts, for a call with room
+        err.needed = (int(call.summary.n_rate_buckets), int(call.summary.n_quant_buckets)) if rc == -28 else None
+        raise err
+    return call.result()
+
+
+def perf_stats_host(events, n_f, qs=PS_DEFAULT_QS, rate_dt_ns=PS_DEFAULT_RATE_DT_NS,
+                    quant_dt_ns=PS_DEFAULT_QUANT_DT_NS, points=True, rate_cap=None, quant_cap=None):
+    """lc_perf_stats_host: the rules of include/lincheck_perf.h on the host ->
+    (a dict of lc_ps_out's arrays: by_f (n_f, 4), rate (n_f, 3, buckets), quant
+    (n_f, buckets, n_q), quant_n (n_f, buckets), comp_pos and latency_ns (None
+    without points); the summary as a dict).  The tables have rule 7's bucket
+    counts unless rate_cap / quant_cap say otherwise; -ENOSPC raises LcError
+    with .needed = (n_rate_buckets, n_quant_buckets)."""
+    return _perf_stats_run(lambda call: lib().lc_perf_stats_host(*call.args()), lambda: "lc_perf_stats_host",
+                           events, n_f, qs, rate_dt_ns, quant_dt_ns, points, rate_cap, quant_cap)
+
+
+def perf_stats_limits():
+    """lc_perf_stats_limits: {"max_f", "max_table_entries", "lds_entries", "default_lds_entries", "wave",
+    "block", "chunk", "max_grid"}."""
+    s = LcPsLimits()
+    rc = lib().lc_perf_stats_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_perf_stats_limits")
+    return {f: getattr(s, f) for f, _ in LcPsLimits._fields_}
+
+
 class Context:
     """An lc_ctx on the GPUs of device_mask (0 = all)."""
 
@@ -1012,6 +1132,13 @@ class Context:
         compares, the forward passes and the backtracks on the device."""
         return _watch_run(lambda call: lib().lc_watch_check(self._h, *call.args()), "lc_watch_check",
                           self.last_error, threads, values, n_nonmonotonic, flags, edit_cap)
+
+    def perf_stats(self, events, n_f, qs=PS_DEFAULT_QS, rate_dt_ns=PS_DEFAULT_RATE_DT_NS,
+                   quant_dt_ns=PS_DEFAULT_QUANT_DT_NS, points=True, rate_cap=None, quant_cap=None):
+        """lc_perf_stats: perf_stats_host's result, with the sorts, the pair
+        pass and the quantile selection on the device."""
+        return _perf_stats_run(lambda call: lib().lc_perf_stats(self._h, *call.args()), self.last_error,
+                               events, n_f, qs, rate_dt_ns, quant_dt_ns, points, rate_cap, quant_cap)
 
     def wr_check(self, txns, mops, wfr_keys=True, edge_cap=None):
         """lc_wr_check: wr_check_host's result, with rules 1-8 on the device."""

@@ -336,4 +336,5 @@ struct lc_ctx {
   lcrt::SideState aps;     // lc_append_check
   lcrt::SideState wrs;     // lc_wr_check
   lcrt::SideState wts;     // lc_watch_check
+  lcrt::SideState pfs;     // lc_perf_stats
 };
