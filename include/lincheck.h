@@ -581,5 +581,7 @@ const char *lc_build_id(void);
 #include "lincheck_watch.h"
 /* lc_perf_stats: the composed checker's :stats and :perf keys on the device */
 #include "lincheck_perf.h"
+/* lc_cycle_screen: a transaction graph proved free of cycles on the device */
+#include "lincheck_screen.h"
 
 #endif /* LINCHECK_H */

@@ -283,6 +283,26 @@ class LcWrLimits(ctypes.Structure):
                 ("max_position", ctypes.c_int64), ("max_mops", ctypes.c_int64)]
 
 
+# lc_cycle_screen (include/lincheck_screen.h): the txn and edge records are
+# list-append's
+LC_SCREEN_RT, LC_SCREEN_TRIM = 1, 2
+
+
+class LcScreenOut(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_void_p) for f in ("reach_lo", "reach_hi", "mark")]
+
+
+class LcScreenSummary(ctypes.Structure):
+    _fields_ = [("clean", ctypes.c_int32), ("label_rounds", ctypes.c_int32), ("trim_rounds", ctypes.c_int32),
+                ("max_rounds", ctypes.c_int32), ("n_rt_members", ctypes.c_int64),
+                ("n_trim_survivors", ctypes.c_int64), ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double),
+                ("total_ms", ctypes.c_double)]
+
+
+class LcScreenLimits(ctypes.Structure):
+    _fields_ = [("max_rounds", ctypes.c_int32), ("default_max_rounds", ctypes.c_int32)]
+
+
 # lc_watch_check (include/lincheck_watch.h)
 LC_WT_DELETE, LC_WT_INSERT = 0, 1
 LC_WT_NO_SCRIPT = 1
@@ -512,6 +532,22 @@ def lib():
             L.lc_perf_stats.restype = ctypes.c_int
             L.lc_perf_stats_limits.argtypes = [ctypes.POINTER(LcPsLimits)]
             L.lc_perf_stats_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_cycle_screen"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            sc = [p, i64, p, i64, ctypes.POINTER(LcScreenOut), ctypes.POINTER(LcScreenSummary)]
+            L.lc_cycle_screen_host.argtypes = sc
+            L.lc_cycle_screen_host.restype = ctypes.c_int
+            L.lc_cycle_screen.argtypes = [vp] + sc
+            L.lc_cycle_screen.restype = ctypes.c_int
+            L.lc_screen_limits.argtypes = [ctypes.POINTER(LcScreenLimits)]
+            L.lc_screen_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_append_check_screened"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            scr = ctypes.POINTER(LcScreenSummary)
+            L.lc_append_check_screened.argtypes = [vp, p, i64, p, i64, p, i64, ctypes.POINTER(LcApOut),
+                                                   ctypes.POINTER(LcApSummary), scr]
+            L.lc_append_check_screened.restype = ctypes.c_int
+            L.lc_wr_check_screened.argtypes = [vp, p, i64, p, i64, ctypes.c_uint32, ctypes.POINTER(LcWrOut),
+                                               ctypes.POINTER(LcWrSummary), scr]
+            L.lc_wr_check_screened.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -795,6 +831,57 @@ def wr_limits():
     if rc != 0:
         raise LcError(rc, "lc_wr_limits")
     return {f: getattr(s, f) for f, _ in LcWrLimits._fields_}
+
+
+def has_screened():
+    """Whether the loaded library has the screened checker calls (a LINCHECK_LIB may lack them)."""
+    return hasattr(lib(), "lc_append_check_screened")
+
+
+def _screen_dict(s):
+    return {f: getattr(s, f) for f, _ in LcScreenSummary._fields_}
+
+
+class _ScreenCall:
+    """One lc_cycle_screen(_host) call's arrays: the inputs made contiguous,
+    the three output arrays, one entry per txn."""
+
+    def __init__(self, txns, edges):
+        self.txns = np.ascontiguousarray(txns, dtype=AP_TXN_DTYPE)
+        self.edges = np.ascontiguousarray(edges, dtype=AP_EDGE_DTYPE)
+        nt = max(len(self.txns), 1)
+        self.arrays = {f: np.zeros(nt, dtype=np.int32) for f in ("reach_lo", "reach_hi", "mark")}
+        self.out = LcScreenOut(**{k: _ptr(v) for k, v in self.arrays.items()})
+        self.summary = LcScreenSummary()
+
+    def args(self):
+        return (_ptr(self.txns), len(self.txns), _ptr(self.edges), len(self.edges), ctypes.byref(self.out),
+                ctypes.byref(self.summary))
+
+    def result(self):
+        """-> (a dict of the output arrays, the summary as a dict)."""
+        nt = len(self.txns)
+        return ({k: v[:nt] for k, v in self.arrays.items()},
+                {f: getattr(self.summary, f) for f, _ in LcScreenSummary._fields_})
+
+
+def cycle_screen_host(txns, edges):
+    """lc_cycle_screen_host: the screen of include/lincheck_screen.h on the host
+    -> ({"reach_lo", "reach_hi", "mark"}, the summary as a dict)."""
+    call = _ScreenCall(txns, edges)
+    rc = lib().lc_cycle_screen_host(*call.args())
+    if rc != 0:
+        raise LcError(rc, "lc_cycle_screen_host")
+    return call.result()
+
+
+def screen_limits():
+    """lc_screen_limits: {"max_rounds", "default_max_rounds"}."""
+    s = LcScreenLimits()
+    rc = lib().lc_screen_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_screen_limits")
+    return {f: getattr(s, f) for f, _ in LcScreenLimits._fields_}
 
 
 class _WatchCall:
@@ -1127,6 +1214,25 @@ class Context:
             raise LcError(rc, self.last_error() if rc in (-22, -7) else "lc_append_check")
         return call.result()
 
+    def append_check_screened(self, txns, mops, values):
+        """lc_append_check_screened: append_check's result, and the screen's
+        summary as a third value; rule 7 runs on the host only where the
+        screen did not prove the graph clean."""
+        call, scr = _AppendCall(txns, mops, values), LcScreenSummary()
+        rc = lib().lc_append_check_screened(self._h, *call.args(), ctypes.byref(scr))
+        if rc != 0:
+            raise LcError(rc, self.last_error() if rc in (-22, -7) else "lc_append_check_screened")
+        return call.result() + (_screen_dict(scr),)
+
+    def wr_check_screened(self, txns, mops, wfr_keys=True, edge_cap=None):
+        """lc_wr_check_screened: wr_check's result, and the screen's summary as
+        a third value; rule 9 runs on the host only where the screen did not
+        prove the graph clean."""
+        scr = LcScreenSummary()
+        out, s = _wr_run(lambda call: lib().lc_wr_check_screened(self._h, *call.args(), ctypes.byref(scr)),
+                         "lc_wr_check_screened", self.last_error, txns, mops, wfr_keys, edge_cap)
+        return out, s, _screen_dict(scr)
+
     def watch_check(self, threads, values, n_nonmonotonic=0, flags=0, edit_cap=None):
         """lc_watch_check: watch_check_host's result, with the hashes, the
         compares, the forward passes and the backtracks on the device."""
@@ -1144,6 +1250,14 @@ class Context:
         """lc_wr_check: wr_check_host's result, with rules 1-8 on the device."""
         return _wr_run(lambda call: lib().lc_wr_check(self._h, *call.args()), "lc_wr_check", self.last_error,
                        txns, mops, wfr_keys, edge_cap)
+
+    def cycle_screen(self, txns, edges):
+        """lc_cycle_screen: cycle_screen_host's result, computed on the device."""
+        call = _ScreenCall(txns, edges)
+        rc = lib().lc_cycle_screen(self._h, *call.args())
+        if rc != 0:
+            raise LcError(rc, self.last_error() if rc == -22 else "lc_cycle_screen")
+        return call.result()
 
     def set_full(self, adds, reads, read_values, linearizable=True):
         """lc_set_full: set_full_host's result, computed on the device."""

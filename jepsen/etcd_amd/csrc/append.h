@@ -69,7 +69,8 @@ using lcgraph::real_time_host;
 // scc_class, steps, cycle_off, cycle_scc, and every field of sum but the
 // read counts (taken from counts[kCounters]), n_slow_reads and the device times.
 void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
-                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum);
+                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum,
+                       bool no_scc = false);  // no_scc: the caller knows of no nontrivial SCC, and rule 7 only fills
 
 #if defined(__HIPCC__)
 // One call's device workspace.

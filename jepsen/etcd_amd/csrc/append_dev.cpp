@@ -8,6 +8,7 @@
 
 #include "append.h"
 #include "runtime.h"
+#include "screen.h"
 
 using namespace lcrt;
 
@@ -21,7 +22,8 @@ struct Pinned {
 };
 
 int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
-                  const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum) {
+                  const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum,
+                  lc_screen_summary *scr) {  // scr: null, or lc_append_check_screened's
   const auto t0 = std::chrono::steady_clock::now();
   lcap::Prep p;
   const char *why = nullptr;
@@ -29,7 +31,10 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
     set_err(c, std::string("lc_append_check: ") + why);
     return -EINVAL;
   }
-  if (n_txns == 0) return lc_append_check_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
+  if (n_txns == 0) {
+    if (scr) *scr = lcscreen::empty_summary();
+    return lc_append_check_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
+  }
   const size_t nt = (size_t)n_txns, nm = (size_t)n_mops, nr = p.rd_mop.size();
   const int64_t n_work = p.work_off[nr];
   lc_ap_limit_info lim;
@@ -168,6 +173,11 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   HIP_TRY(c, hipMemcpyAsync(out->rt_hi, rt.rt_hi, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   const int64_t n_edges = h.count[1];
+  // the screen, on the edges and ranges where they stand: a clean graph spares rule 7
+  lc_screen_summary scs{};
+  if (scr)
+    if (int e = lcscreen::screen_resident(c, st, w.txns, n_txns, p.n_ok, d_edges_a, n_edges, rt.byc, rt.rt_hi, &scs))
+      return e;
   if (n_edges > 0) {  // only the unique edges reach the caller
     HIP_TRY(c, hipMemcpyAsync(out->edges, d_edges_a, sizeof(lc_ap_edge) * (size_t)n_edges, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
@@ -202,13 +212,14 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
     }
   }
   lc_ap_summary sm;
-  lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm);
+  lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm, scr && scs.clean == 1);
   sm.n_slow_reads = n_slow;
   sm.h2d_ms = elapsed_ms(e0, e1);
   sm.kernel_ms = elapsed_ms(k0, k1);
   sm.kernel_ms += elapsed_ms(k2, e2);
   sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = sm;
+  if (scr) *scr = scs;
   return 0;
 }
 
@@ -219,5 +230,15 @@ extern "C" int lc_append_check(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns,
                                lc_ap_summary *sum) {
   if (!c) return -EINVAL;
   return no_bad_alloc(c, "lc_append_check",
-                      [&] { return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum); });
+                      [&] { return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum, nullptr); });
+}
+
+extern "C" int lc_append_check_screened(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops,
+                                        int64_t n_mops, const int64_t *values, int64_t n_values, const lc_ap_out *out,
+                                        lc_ap_summary *sum, lc_screen_summary *scr) {
+  if (!c) return -EINVAL;
+  lc_screen_summary local;
+  return no_bad_alloc(c, "lc_append_check_screened", [&] {
+    return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum, scr ? scr : &local);
+  });
 }

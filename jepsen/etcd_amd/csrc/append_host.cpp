@@ -158,12 +158,15 @@ int64_t rules34_direct(const lc_ap_txn *txns, const lc_ap_mop *mops, const int64
 }
 
 void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
-                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum) {
+                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum, bool no_scc) {
   const auto t0 = std::chrono::steady_clock::now();
   lc_ap_summary s{};
   lcgraph::CycleCounts cc;
-  lcgraph::cycles_host(txns, n_txns, p.n_nodes, out->edges, n_edges, out->byc, out->rt_lo, out->rt_hi, out->scc,
-                       out->scc_class, out->steps, out->cycle_off, out->cycle_scc, &cc);
+  if (no_scc)
+    lcgraph::no_cycles(n_txns, out->scc, out->scc_class, out->cycle_off, out->cycle_scc, &cc);
+  else
+    lcgraph::cycles_host(txns, n_txns, p.n_nodes, out->edges, n_edges, out->byc, out->rt_lo, out->rt_hi, out->scc,
+                         out->scc_class, out->steps, out->cycle_off, out->cycle_scc, &cc);
   std::copy(cc.n_class, cc.n_class + 8, s.n_class);
   for (int64_t k = 0; k < n_keys; k++)
     if (out->keys[k].flags & LC_AP_K_INCOMPATIBLE) s.n_incompatible_order++;

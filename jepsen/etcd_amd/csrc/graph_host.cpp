@@ -263,4 +263,12 @@ void cycles_host(const lc_ap_txn *txns, int64_t n_txns, int64_t n_nodes, const l
   *counts = s;
 }
 
+void no_cycles(int64_t n_txns, int32_t *scc, int32_t *scc_class, int64_t *cycle_off, int32_t *cycle_scc,
+               CycleCounts *counts) {
+  for (int64_t t = 0; t < n_txns; t++) scc[t] = scc_class[t] = -1;
+  for (int i = 0; i <= LC_AP_MAX_CYCLES; i++) cycle_off[i] = 0;
+  for (int i = 0; i < LC_AP_MAX_CYCLES; i++) cycle_scc[i] = -1;
+  *counts = CycleCounts{};
+}
+
 }  // namespace lcgraph

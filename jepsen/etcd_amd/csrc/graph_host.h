@@ -29,4 +29,10 @@ void cycles_host(const lc_ap_txn *txns, int64_t n_txns, int64_t n_nodes, const l
                  const int32_t *byc, const int32_t *rt_lo, const int32_t *rt_hi, int32_t *scc, int32_t *scc_class,
                  lc_ap_step *steps, int64_t *cycle_off, int32_t *cycle_scc, CycleCounts *counts);
 
+// What cycles_host writes for a graph without a nontrivial SCC, for a caller
+// that knows there is none (lc_cycle_screen's clean = 1): scc and scc_class
+// all -1, cycle_off all 0, cycle_scc all -1, no counts.
+void no_cycles(int64_t n_txns, int32_t *scc, int32_t *scc_class, int64_t *cycle_off, int32_t *cycle_scc,
+               CycleCounts *counts);
+
 }  // namespace lcgraph

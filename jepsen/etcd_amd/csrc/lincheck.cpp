@@ -1395,6 +1395,7 @@ void lc_close(lc_ctx *c) {
     release(c->wrs);
     release(c->wts);
     release(c->pfs);
+    release(c->scs);
   }
   for (auto &f : c->fxs) lc_fx_close(f.first);
   if (c->fx_all) lc_fx_close(c->fx_all);

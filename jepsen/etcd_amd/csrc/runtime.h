@@ -337,4 +337,5 @@ struct lc_ctx {
   lcrt::SideState wrs;     // lc_wr_check
   lcrt::SideState wts;     // lc_watch_check
   lcrt::SideState pfs;     // lc_perf_stats
+  lcrt::SideState scs;     // lc_cycle_screen
 };

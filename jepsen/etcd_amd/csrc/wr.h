@@ -37,7 +37,8 @@ int prepare(const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_
 // n_edges_raw and the device times.  counts[kCounters] are the read counts
 // and the lost-update versions.
 void graph_and_summary(const lc_wr_txn *txns, int64_t n_txns, const Prep &p, const lc_wr_out *out, int64_t n_keys,
-                       int64_t n_edges, const int64_t *counts, lc_wr_summary *sum);
+                       int64_t n_edges, const int64_t *counts, lc_wr_summary *sum,
+                       bool no_scc = false);  // no_scc: the caller knows of no nontrivial SCC, and rule 9 only fills
 
 #if defined(__HIPCC__)
 // One call's device workspace.

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "runtime.h"
+#include "screen.h"
 #include "wr.h"
 
 using namespace lcrt;
@@ -22,7 +23,8 @@ struct Pinned {
 };
 
 int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_t n_mops,
-              uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum) {
+              uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum,
+              lc_screen_summary *scr) {  // scr: null, or lc_wr_check_screened's
   const auto t0 = std::chrono::steady_clock::now();
   lcwr::Prep p;
   const char *why = nullptr;
@@ -30,7 +32,10 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
     set_err(c, std::string("lc_wr_check: ") + why);
     return -EINVAL;
   }
-  if (n_txns == 0) return lc_wr_check_host(txns, n_txns, mops, n_mops, flags, out, sum);
+  if (n_txns == 0) {
+    if (scr) *scr = lcscreen::empty_summary();
+    return lc_wr_check_host(txns, n_txns, mops, n_mops, flags, out, sum);
+  }
   lc_wr_limit_info lim;
   lc_wr_limits(&lim);
   if (n_mops > lim.max_mops) {  // (a table slot's index is an int32)
@@ -228,6 +233,11 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
     }
     return -ENOSPC;
   }
+  // the screen, on the edges and ranges where they stand: a clean graph spares rule 9
+  lc_screen_summary scs{};
+  if (scr)
+    if (int e = lcscreen::screen_resident(c, st, w.txns, n_txns, p.n_ok, d_edges_b, n_edges, rt.byc, rt.rt_hi, &scs))
+      return e;
   if (nm) HIP_TRY(c, hipMemcpyAsync(out->mop_flags, w.mop_flags, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(out->txn_flags, w.txn_flags, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
   if (n_keys)
@@ -242,13 +252,14 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
   int64_t counts[lcwr::kCounters];
   for (int b = 0; b < lcwr::kCounters; b++) counts[b] = lcwr::sum_counters(h.counters, b);
   lc_wr_summary sm;
-  lcwr::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, counts, &sm);
+  lcwr::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, counts, &sm, scr && scs.clean == 1);
   sm.n_edges_raw = n_sel;
   sm.h2d_ms = elapsed_ms(e0, e1);
   sm.kernel_ms = elapsed_ms(k0, k1);
   sm.kernel_ms += elapsed_ms(k2, e2);
   sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = sm;
+  if (scr) *scr = scs;
   return 0;
 }
 
@@ -257,5 +268,16 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
 extern "C" int lc_wr_check(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_t n_mops,
                            uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum) {
   if (!c) return -EINVAL;
-  return no_bad_alloc(c, "lc_wr_check", [&] { return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum); });
+  return no_bad_alloc(c, "lc_wr_check",
+                      [&] { return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum, nullptr); });
+}
+
+extern "C" int lc_wr_check_screened(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops,
+                                    int64_t n_mops, uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum,
+                                    lc_screen_summary *scr) {
+  if (!c) return -EINVAL;
+  lc_screen_summary local;
+  return no_bad_alloc(c, "lc_wr_check_screened", [&] {
+    return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum, scr ? scr : &local);
+  });
 }

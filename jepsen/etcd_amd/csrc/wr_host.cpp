@@ -58,12 +58,15 @@ int prepare(const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_
 }
 
 void graph_and_summary(const lc_wr_txn *txns, int64_t n_txns, const Prep &p, const lc_wr_out *out, int64_t n_keys,
-                       int64_t n_edges, const int64_t *counts, lc_wr_summary *sum) {
+                       int64_t n_edges, const int64_t *counts, lc_wr_summary *sum, bool no_scc) {
   const auto t0 = std::chrono::steady_clock::now();
   lc_wr_summary s{};
   lcgraph::CycleCounts cc;
-  lcgraph::cycles_host(txns, n_txns, p.n_nodes, out->edges, n_edges, out->byc, out->rt_lo, out->rt_hi, out->scc,
-                       out->scc_class, out->steps, out->cycle_off, out->cycle_scc, &cc);
+  if (no_scc)
+    lcgraph::no_cycles(n_txns, out->scc, out->scc_class, out->cycle_off, out->cycle_scc, &cc);
+  else
+    lcgraph::cycles_host(txns, n_txns, p.n_nodes, out->edges, n_edges, out->byc, out->rt_lo, out->rt_hi, out->scc,
+                         out->scc_class, out->steps, out->cycle_off, out->cycle_scc, &cc);
   std::copy(cc.n_class, cc.n_class + 8, s.n_class);
   bool lost = false;
   for (int64_t k = 0; k < n_keys; k++) {

@@ -248,11 +248,20 @@ class WrChecker:
     device=True works on the first GPU of device_mask (lc_wr_check: the
     library must have it; there is no quiet fallback); device=False uses
     lc_wr_check_host and needs no GPU.
+
+    device_scc=True uses lc_wr_check_screened (include/lincheck_screen.h): the
+    cycle screen runs on the device, the host's SCC pass only where it does
+    not prove the graph clean, and the result map gains an "scc-screen"
+    sub-map (clean, rounds, members, ms); every other key is unchanged.  With
+    a library that lacks the call the unscreened one runs and the sub-map is
+    absent.  Off by default.
     """
 
-    def __init__(self, device_mask=0, device=True, wfr_keys=True):
+    def __init__(self, device_mask=0, device=True, wfr_keys=True, device_scc=False):
         self.device_mask = device_mask
         self.device = device
+        self.device_scc = device_scc
+        self.last_screen = None   # device_scc: the screen's lc_screen_summary of the last check, as a dict
         self.wfr_keys = wfr_keys
         self._ctx = None
         self.last_summary = None  # the library's lc_wr_summary of the last check, as a dict
@@ -272,11 +281,25 @@ class WrChecker:
         history = list(history)
         enc = encode(history)
         if self.device:
-            out, s = self._context().wr_check(enc.txns, enc.mops, self.wfr_keys)
+            scr = None
+            if self.device_scc and abi.has_screened():
+                out, s, scr = self._context().wr_check_screened(enc.txns, enc.mops, self.wfr_keys)
+            else:  # (a library without the screened call: the unscreened one, and no sub-map)
+                out, s = self._context().wr_check(enc.txns, enc.mops, self.wfr_keys)
+            self.last_screen = scr
         else:
+            self.last_screen = None
             out, s = abi.wr_check_host(enc.txns, enc.mops, self.wfr_keys)
         self.last_out, self.last_summary = out, s
-        return result_map(history, enc, out, s, self.wfr_keys)
+        result = result_map(history, enc, out, s, self.wfr_keys)
+        if self.device and self.last_screen is not None:
+            scr = self.last_screen
+            result["scc-screen"] = {"clean": {1: True, 0: False, -1: "gave-up"}[scr["clean"]],
+                                    "label-rounds": scr["label_rounds"], "trim-rounds": scr["trim_rounds"],
+                                    "max-rounds": scr["max_rounds"], "rt-members": scr["n_rt_members"],
+                                    "trim-survivors": scr["n_trim_survivors"], "kernel-ms": scr["kernel_ms"],
+                                    "ms": scr["total_ms"]}
+        return result
 
 
 def synth_arrays(n_txns, seed=0, live_keys=3, per_key=32, max_mops=4, concurrency=10, p_info=0.03):
