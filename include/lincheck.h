@@ -583,5 +583,7 @@ const char *lc_build_id(void);
 #include "lincheck_perf.h"
 /* lc_cycle_screen: a transaction graph proved free of cycles on the device */
 #include "lincheck_screen.h"
+/* lc_cycle_reach: the txn that closes a G-single cycle, searched on the device */
+#include "lincheck_cycles.h"
 
 #endif /* LINCHECK_H */

@@ -303,6 +303,33 @@ class LcScreenLimits(ctypes.Structure):
     _fields_ = [("max_rounds", ctypes.c_int32), ("default_max_rounds", ctypes.c_int32)]
 
 
+# lc_cycle_reach and the restricted checker calls (include/lincheck_cycles.h)
+LC_REACH_ALL = 1
+
+
+class LcReachSummary(ctypes.Structure):
+    _fields_ = [("first_hit", ctypes.c_int64), ("n_queries_run", ctypes.c_int64), ("nodes_visited", ctypes.c_int64),
+                ("h2d_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
+class LcReachLimits(ctypes.Structure):
+    _fields_ = [("max_nodes", ctypes.c_int64), ("min_work", ctypes.c_int64), ("default_min_work", ctypes.c_int64),
+                ("max_workgroups", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class LcCycleSearchSummary(ctypes.Structure):
+    _fields_ = [("restricted", ctypes.c_int32), ("pad", ctypes.c_int32), ("n_marked", ctypes.c_int64),
+                ("n_device_searches", ctypes.c_int64), ("n_device_queries", ctypes.c_int64),
+                ("n_host_fallbacks", ctypes.c_int64), ("search_ms", ctypes.c_double)]
+
+
+# lc_cycles_host's hook: (user, n_nodes, pred_off, pred, n_queries, q_node, q_head_off, q_heads, first_hit) -> int
+LC_REACH_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                               ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(ctypes.c_int64))
+
+
 # lc_watch_check (include/lincheck_watch.h)
 LC_WT_DELETE, LC_WT_INSERT = 0, 1
 LC_WT_NO_SCRIPT = 1
@@ -548,6 +575,25 @@ def lib():
             L.lc_wr_check_screened.argtypes = [vp, p, i64, p, i64, ctypes.c_uint32, ctypes.POINTER(LcWrOut),
                                                ctypes.POINTER(LcWrSummary), scr]
             L.lc_wr_check_screened.restype = ctypes.c_int
+        if hasattr(L, "lc_cycle_reach"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            rs = [i64, p, p, i64, i64, p, p, p, i64, ctypes.c_uint32, p, ctypes.POINTER(LcReachSummary)]
+            L.lc_cycle_reach_host.argtypes = rs
+            L.lc_cycle_reach_host.restype = ctypes.c_int
+            L.lc_cycle_reach.argtypes = [vp] + rs
+            L.lc_cycle_reach.restype = ctypes.c_int
+            L.lc_cycle_reach_limits.argtypes = [ctypes.POINTER(LcReachLimits)]
+            L.lc_cycle_reach_limits.restype = ctypes.c_int
+            L.lc_cycles_host.argtypes = [p, i64, p, i64, p, LC_REACH_FN, p, i64, i64, p, p, p, p, p, p, p,
+                                         ctypes.POINTER(LcCycleSearchSummary)]
+            L.lc_cycles_host.restype = ctypes.c_int
+        if hasattr(L, "lc_append_check_restricted"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            scr, srch = ctypes.POINTER(LcScreenSummary), ctypes.POINTER(LcCycleSearchSummary)
+            L.lc_append_check_restricted.argtypes = [vp, p, i64, p, i64, p, i64, ctypes.POINTER(LcApOut),
+                                                     ctypes.POINTER(LcApSummary), scr, srch]
+            L.lc_append_check_restricted.restype = ctypes.c_int
+            L.lc_wr_check_restricted.argtypes = [vp, p, i64, p, i64, ctypes.c_uint32, ctypes.POINTER(LcWrOut),
+                                                 ctypes.POINTER(LcWrSummary), scr, srch]
+            L.lc_wr_check_restricted.restype = ctypes.c_int
         L.lc_abi_version.argtypes = []
         L.lc_abi_version.restype = ctypes.c_int
         L.lc_synth_register.argtypes = [ctypes.POINTER(LcSynthParams), p, p, p,
@@ -882,6 +928,104 @@ def screen_limits():
     if rc != 0:
         raise LcError(rc, "lc_screen_limits")
     return {f: getattr(s, f) for f, _ in LcScreenLimits._fields_}
+
+
+def has_restricted():
+    """Whether the loaded library has the restricted checker calls (a LINCHECK_LIB may lack them)."""
+    return hasattr(lib(), "lc_append_check_restricted")
+
+
+def _struct_dict(s):
+    return {f: getattr(s, f) for f, _ in s._fields_ if f != "pad"}
+
+
+class _ReachCall:
+    """One lc_cycle_reach(_host) call's arrays: the inputs made contiguous, hit
+    with one entry per query."""
+
+    def __init__(self, n_nodes, pred_off, pred, q_node, q_head_off, q_heads, all_queries):
+        self.n_nodes = int(n_nodes)
+        self.pred_off = np.ascontiguousarray(pred_off, dtype=np.int64)
+        self.pred = np.ascontiguousarray(pred, dtype=np.int32)
+        self.q_node = np.ascontiguousarray(q_node, dtype=np.int32)
+        self.q_head_off = np.ascontiguousarray(q_head_off, dtype=np.int64)
+        self.q_heads = np.ascontiguousarray(q_heads, dtype=np.int32)
+        self.flags = LC_REACH_ALL if all_queries else 0
+        # (-7: what no call writes, so a test can see that nothing was written)
+        self.hit = np.full(max(len(self.q_node), 1), -7, dtype=np.int32)
+        self.summary = LcReachSummary()
+
+    def args(self):
+        return (self.n_nodes, _ptr(self.pred_off), _ptr(self.pred), len(self.pred), len(self.q_node),
+                _ptr(self.q_node), _ptr(self.q_head_off), _ptr(self.q_heads), len(self.q_heads), self.flags,
+                _ptr(self.hit), ctypes.byref(self.summary))
+
+    def result(self):
+        """-> (hit, one entry per query, or None without all_queries; the summary as a dict)."""
+        return (self.hit[:len(self.q_node)] if self.flags else None), _struct_dict(self.summary)
+
+
+def cycle_reach_host(n_nodes, pred_off, pred, q_node, q_head_off, q_heads, all_queries=False):
+    """lc_cycle_reach_host: batched backward reachability, first hit
+    (include/lincheck_cycles.h), on the host -> (hit or None, the summary as a dict)."""
+    call = _ReachCall(n_nodes, pred_off, pred, q_node, q_head_off, q_heads, all_queries)
+    rc = lib().lc_cycle_reach_host(*call.args())
+    if rc != 0:
+        err = LcError(rc, "lc_cycle_reach_host")
+        err.call = call
+        raise err
+    return call.result()
+
+
+def cycle_reach_limits():
+    """lc_cycle_reach_limits: {"max_nodes", "min_work", "default_min_work", "max_workgroups"}."""
+    s = LcReachLimits()
+    rc = lib().lc_cycle_reach_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_cycle_reach_limits")
+    return _struct_dict(s)
+
+
+def cycles_host(txns, edges, mark=None, reach=None, min_work=0, max_nodes=0):
+    """lc_cycles_host: rule 7 alone on the host, over the whole graph (mark
+    None) or over the marked txns; reach(n_nodes, pred_off, pred, q_node,
+    q_head_off, q_heads) -> first_hit answers the class loop's searches in
+    place of the host loop (None: it refuses, and the host loop runs, as it
+    does for a search over more than max_nodes > 0 nodes) -> (a dict of scc, scc_class, steps, cycle_off,
+    cycle_scc, n_class, n_scc; the search summary as a dict)."""
+    txns = np.ascontiguousarray(txns, dtype=AP_TXN_DTYPE)
+    edges = np.ascontiguousarray(edges, dtype=AP_EDGE_DTYPE)
+    nt = max(len(txns), 1)
+    out = {"scc": np.zeros(nt, np.int32), "scc_class": np.zeros(nt, np.int32),
+           "steps": np.zeros(nt, dtype=AP_STEP_DTYPE), "cycle_off": np.zeros(LC_AP_MAX_CYCLES + 1, np.int64),
+           "cycle_scc": np.zeros(LC_AP_MAX_CYCLES, np.int32), "n_class": np.zeros(8, np.int64)}
+    n_scc, srch = ctypes.c_int64(0), LcCycleSearchSummary()
+    if mark is not None:
+        mark = np.ascontiguousarray(mark, dtype=np.int32)
+
+    def hook(_user, n_nodes, pred_off, pred, n_queries, q_node, q_head_off, q_heads, first_hit):
+        po = np.ctypeslib.as_array(pred_off, (n_nodes + 1,))
+        qo = np.ctypeslib.as_array(q_head_off, (n_queries + 1,))
+        pr = np.ctypeslib.as_array(pred, (int(po[-1]),)) if po[-1] else np.zeros(0, np.int32)
+        qh = np.ctypeslib.as_array(q_heads, (int(qo[-1]),)) if qo[-1] else np.zeros(0, np.int32)
+        first = reach(n_nodes, po, pr, np.ctypeslib.as_array(q_node, (n_queries,)), qo, qh)
+        if first is None:
+            return 1
+        first_hit[0] = int(first)
+        return 0
+
+    fn = LC_REACH_FN(hook) if reach is not None else LC_REACH_FN()
+    rc = lib().lc_cycles_host(_ptr(txns), len(txns), _ptr(edges), len(edges), _ptr(mark) if mark is not None else None,
+                              fn, None, int(min_work), int(max_nodes), _ptr(out["scc"]), _ptr(out["scc_class"]),
+                              _ptr(out["steps"]),
+                              _ptr(out["cycle_off"]), _ptr(out["cycle_scc"]), _ptr(out["n_class"]),
+                              ctypes.byref(n_scc), ctypes.byref(srch))
+    if rc != 0:
+        raise LcError(rc, "lc_cycles_host")
+    out["scc"], out["scc_class"] = out["scc"][:len(txns)], out["scc_class"][:len(txns)]
+    out["steps"] = out["steps"][:int(out["cycle_off"][-1])]
+    out["n_scc"] = n_scc.value
+    return out, _struct_dict(srch)
 
 
 class _WatchCall:
@@ -1232,6 +1376,35 @@ class Context:
         out, s = _wr_run(lambda call: lib().lc_wr_check_screened(self._h, *call.args(), ctypes.byref(scr)),
                          "lc_wr_check_screened", self.last_error, txns, mops, wfr_keys, edge_cap)
         return out, s, _screen_dict(scr)
+
+    def append_check_restricted(self, txns, mops, values):
+        """lc_append_check_restricted: append_check_screened's result, and the
+        cycle search's summary as a fourth value; where the screen did not
+        prove the graph clean, rule 7 runs over the marked txns only."""
+        call, scr, srch = _AppendCall(txns, mops, values), LcScreenSummary(), LcCycleSearchSummary()
+        rc = lib().lc_append_check_restricted(self._h, *call.args(), ctypes.byref(scr), ctypes.byref(srch))
+        if rc != 0:
+            raise LcError(rc, self.last_error() if rc in (-22, -7) else "lc_append_check_restricted")
+        return call.result() + (_screen_dict(scr), _struct_dict(srch))
+
+    def wr_check_restricted(self, txns, mops, wfr_keys=True, edge_cap=None):
+        """lc_wr_check_restricted: wr_check_screened's result, and the cycle
+        search's summary as a fourth value."""
+        scr, srch = LcScreenSummary(), LcCycleSearchSummary()
+        out, s = _wr_run(lambda call: lib().lc_wr_check_restricted(self._h, *call.args(), ctypes.byref(scr),
+                                                                   ctypes.byref(srch)),
+                         "lc_wr_check_restricted", self.last_error, txns, mops, wfr_keys, edge_cap)
+        return out, s, _screen_dict(scr), _struct_dict(srch)
+
+    def cycle_reach(self, n_nodes, pred_off, pred, q_node, q_head_off, q_heads, all_queries=False):
+        """lc_cycle_reach: cycle_reach_host's result, computed on the device."""
+        call = _ReachCall(n_nodes, pred_off, pred, q_node, q_head_off, q_heads, all_queries)
+        rc = lib().lc_cycle_reach(self._h, *call.args())
+        if rc != 0:
+            err = LcError(rc, self.last_error() if rc in (-22, -7) else "lc_cycle_reach")
+            err.call = call
+            raise err
+        return call.result()
 
     def watch_check(self, threads, values, n_nonmonotonic=0, flags=0, edit_cap=None):
         """lc_watch_check: watch_check_host's result, with the hashes, the

@@ -68,9 +68,11 @@ using lcgraph::real_time_host;
 // Rule 7 (graph_host.cpp's cycles_host) and rule 8 over finished flags, keys, edges and ranges: out->scc,
 // scc_class, steps, cycle_off, cycle_scc, and every field of sum but the
 // read counts (taken from counts[kCounters]), n_slow_reads and the device times.
-void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
-                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum,
-                       bool no_scc = false);  // no_scc: the caller knows of no nontrivial SCC, and rule 7 only fills
+// no_scc: the caller knows of no nontrivial SCC, and rule 7 only fills.  mp: rule 7 runs over the marked txns
+// (cycles_host_marked); its error, the hook's, is returned and *sum is then not written.  0 otherwise.
+int graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
+                      int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum,
+                      bool no_scc = false, lcgraph::MarkedPass *mp = nullptr);
 
 #if defined(__HIPCC__)
 // One call's device workspace.

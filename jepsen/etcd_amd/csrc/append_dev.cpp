@@ -9,6 +9,7 @@
 #include "append.h"
 #include "runtime.h"
 #include "screen.h"
+#include "cycles.h"
 
 using namespace lcrt;
 
@@ -23,7 +24,9 @@ struct Pinned {
 
 int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops, int64_t n_mops,
                   const int64_t *values, int64_t n_values, const lc_ap_out *out, lc_ap_summary *sum,
-                  lc_screen_summary *scr) {  // scr: null, or lc_append_check_screened's
+                  lc_screen_summary *scr,  // scr: null, or lc_append_check_screened's
+                  lc_cycle_search_summary *srch = nullptr,
+                  bool restricted = false) {  // lc_append_check_restricted: rule 7 over the screen's marks
   const auto t0 = std::chrono::steady_clock::now();
   lcap::Prep p;
   const char *why = nullptr;
@@ -32,8 +35,10 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
     return -EINVAL;
   }
   if (n_txns == 0) {
-    if (scr) *scr = lcscreen::empty_summary();
-    return lc_append_check_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
+    const int e = lc_append_check_host(txns, n_txns, mops, n_mops, values, n_values, out, sum);
+    if (!e && scr) *scr = lcscreen::empty_summary();
+    if (!e && srch) *srch = lccyc::search_summary(nullptr);
+    return e;
   }
   const size_t nt = (size_t)n_txns, nm = (size_t)n_mops, nr = p.rd_mop.size();
   const int64_t n_work = p.work_off[nr];
@@ -175,8 +180,10 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   const int64_t n_edges = h.count[1];
   // the screen, on the edges and ranges where they stand: a clean graph spares rule 7
   lc_screen_summary scs{};
+  std::vector<int32_t> mark(restricted ? nt : 0);
   if (scr)
-    if (int e = lcscreen::screen_resident(c, st, w.txns, n_txns, p.n_ok, d_edges_a, n_edges, rt.byc, rt.rt_hi, &scs))
+    if (int e = lcscreen::screen_resident(c, st, w.txns, n_txns, p.n_ok, d_edges_a, n_edges, rt.byc, rt.rt_hi, &scs,
+                                          restricted ? mark.data() : nullptr))
       return e;
   if (n_edges > 0) {  // only the unique edges reach the caller
     HIP_TRY(c, hipMemcpyAsync(out->edges, d_edges_a, sizeof(lc_ap_edge) * (size_t)n_edges, hipMemcpyDeviceToHost, st));
@@ -212,7 +219,12 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
     }
   }
   lc_ap_summary sm;
-  lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm, scr && scs.clean == 1);
+  // not proved clean, and neither phase gave up: every member of an SCC is marked
+  lcgraph::MarkedPass mp, *marked = restricted && scs.clean == 0 ? &mp : nullptr;
+  if (marked) lccyc::device_pass(c, mark.data(), marked);
+  if (int e = lcap::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, n_nonprefix, counts, &sm,
+                                      scr && scs.clean == 1, marked))
+    return e;
   sm.n_slow_reads = n_slow;
   sm.h2d_ms = elapsed_ms(e0, e1);
   sm.kernel_ms = elapsed_ms(k0, k1);
@@ -220,6 +232,7 @@ int append_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
   sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = sm;
   if (scr) *scr = scs;
+  if (srch) *srch = lccyc::search_summary(marked);
   return 0;
 }
 
@@ -240,5 +253,16 @@ extern "C" int lc_append_check_screened(lc_ctx *c, const lc_ap_txn *txns, int64_
   lc_screen_summary local;
   return no_bad_alloc(c, "lc_append_check_screened", [&] {
     return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum, scr ? scr : &local);
+  });
+}
+
+extern "C" int lc_append_check_restricted(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_mop *mops,
+                                          int64_t n_mops, const int64_t *values, int64_t n_values,
+                                          const lc_ap_out *out, lc_ap_summary *sum, lc_screen_summary *scr,
+                                          lc_cycle_search_summary *srch) {
+  if (!c) return -EINVAL;
+  lc_screen_summary local;
+  return no_bad_alloc(c, "lc_append_check_restricted", [&] {
+    return append_device(c, txns, n_txns, mops, n_mops, values, n_values, out, sum, scr ? scr : &local, srch, true);
   });
 }

@@ -157,14 +157,20 @@ int64_t rules34_direct(const lc_ap_txn *txns, const lc_ap_mop *mops, const int64
   return n;
 }
 
-void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
-                       int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum, bool no_scc) {
+int graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, const lc_ap_out *out, int64_t n_keys,
+                      int64_t n_edges, int64_t n_nonprefix, const int64_t *counts, lc_ap_summary *sum, bool no_scc,
+                      lcgraph::MarkedPass *mp) {
   const auto t0 = std::chrono::steady_clock::now();
   lc_ap_summary s{};
   lcgraph::CycleCounts cc;
   if (no_scc)
     lcgraph::no_cycles(n_txns, out->scc, out->scc_class, out->cycle_off, out->cycle_scc, &cc);
-  else
+  else if (mp) {
+    if (int e = lcgraph::cycles_host_marked(txns, n_txns, out->edges, n_edges, out->byc, p.n_ok, out->rt_lo, out->rt_hi,
+                                            mp, out->scc, out->scc_class, out->steps, out->cycle_off, out->cycle_scc,
+                                            &cc))
+      return e;
+  } else
     lcgraph::cycles_host(txns, n_txns, p.n_nodes, out->edges, n_edges, out->byc, out->rt_lo, out->rt_hi, out->scc,
                          out->scc_class, out->steps, out->cycle_off, out->cycle_scc, &cc);
   std::copy(cc.n_class, cc.n_class + 8, s.n_class);
@@ -187,6 +193,7 @@ void graph_and_summary(const lc_ap_txn *txns, int64_t n_txns, const Prep &p, con
   s.valid = p.n_ok == 0 ? -1 : bad ? 0 : 1;
   s.host_graph_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = s;
+  return 0;
 }
 
 }  // namespace lcap

@@ -4,7 +4,10 @@
 // g++, no GPU.
 #include "graph_host.h"
 
+#include <errno.h>
+
 #include <algorithm>
+#include <chrono>
 #include <utility>
 #include <vector>
 
@@ -261,6 +264,242 @@ void cycles_host(const lc_ap_txn *txns, int64_t n_txns, int64_t n_nodes, const l
   s.n_scc = (int64_t)members.size();
   s.n_cycles_returned = n_cycles;
   *counts = s;
+}
+
+namespace {
+
+// The marked txns as a graph of their own: local ids in txn order, the edges
+// with both ends marked under those ids (still sorted: the renaming is
+// monotone), and real time's ranges over the marked OK txns by comp_pos.
+// byc is the stable sort of the OK txns by comp_pos, so its marked entries
+// are the stable sort of the marked OK txns, and the entries before index i
+// of it are the txns below (comp_pos, txn) of byc[i].
+struct MarkedGraph {
+  std::vector<int32_t> ids;  // local -> txn
+  std::vector<lc_ap_edge> edges;
+  std::vector<int32_t> byc, lo, hi;
+
+  int32_t local(int32_t t) const {  // -1: not marked
+    const auto it = std::lower_bound(ids.begin(), ids.end(), t);
+    return it != ids.end() && *it == t ? (int32_t)(it - ids.begin()) : -1;
+  }
+
+  void build(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_edge *all, int64_t n_edges, const int32_t *full_byc,
+             int64_t n_ok, const int32_t *rt_lo, const int32_t *rt_hi, const int32_t *mark) {
+    for (int64_t t = 0; t < n_txns; t++)
+      if (mark[t] && txns[t].type != LC_AP_FAIL) ids.push_back((int32_t)t);
+    const size_t m = ids.size();
+    // the edges are sorted by from: a marked txn's out-edges by two binary searches
+    for (size_t u = 0; u < m; u++) {
+      const int32_t t = ids[u];
+      const lc_ap_edge *e = std::lower_bound(all, all + n_edges, t, [](const lc_ap_edge &x, int32_t f) { return x.from < f; });
+      for (; e < all + n_edges && e->from == t; e++) {
+        const int32_t v = local(e->to);
+        if (v >= 0) edges.push_back(lc_ap_edge{(int32_t)u, v, e->type, 0, e->key});
+      }
+    }
+    std::vector<int32_t> ok;  // marked OK txns (local), by (comp_pos, txn)
+    for (size_t u = 0; u < m; u++)
+      if (txns[ids[u]].type == LC_AP_OK) ok.push_back((int32_t)u);
+    std::stable_sort(ok.begin(), ok.end(),
+                     [&](int32_t a, int32_t b) { return txns[ids[(size_t)a]].comp_pos < txns[ids[(size_t)b]].comp_pos; });
+    byc = ok;
+    // the marked entries of full_byc before its index i
+    auto before = [&](int64_t i) -> int32_t {
+      if (i >= n_ok) return (int32_t)ok.size();
+      const int32_t bt = full_byc[i];
+      const int32_t bc = txns[bt].comp_pos;
+      return (int32_t)(std::lower_bound(ok.begin(), ok.end(), 0,
+                                        [&](int32_t a, int) {
+                                          const int32_t at = ids[(size_t)a];
+                                          return txns[at].comp_pos < bc || (txns[at].comp_pos == bc && at < bt);
+                                        }) -
+                       ok.begin());
+    };
+    lo.resize(m);
+    hi.resize(m);
+    for (size_t u = 0; u < m; u++) {
+      const int32_t t = ids[u];
+      lo[u] = hi[u] = 0;
+      if (rt_hi[t] <= rt_lo[t]) continue;
+      lo[u] = before(rt_lo[t]);
+      hi[u] = before(rt_hi[t]);
+    }
+  }
+};
+
+}  // namespace
+
+int cycles_host_marked(const lc_ap_txn *txns, int64_t n_txns, const lc_ap_edge *edges, int64_t n_edges,
+                       const int32_t *byc, int64_t n_ok, const int32_t *rt_lo, const int32_t *rt_hi, MarkedPass *mp,
+                       int32_t *scc, int32_t *scc_class, lc_ap_step *out_steps, int64_t *cycle_off,
+                       int32_t *cycle_scc, CycleCounts *counts) {
+  CycleCounts s{};
+  for (int64_t t = 0; t < n_txns; t++) scc[t] = scc_class[t] = -1;
+  MarkedGraph mg;
+  mg.build(txns, n_txns, edges, n_edges, byc, n_ok, rt_lo, rt_hi, mp->mark);
+  const std::vector<int32_t> &ids = mg.ids;
+  const size_t m = ids.size();
+  mp->n_marked = (int64_t)m;
+  Graph g;
+  g.n = (int64_t)m;
+  g.edges = mg.edges.data();
+  g.n_edges = (int64_t)mg.edges.size();
+  g.byc = mg.byc.data();
+  g.lo = mg.lo.data();
+  g.hi = mg.hi.data();
+  g.init();
+  std::vector<int32_t> nodes(m), lscc(m, -1);  // lscc: scc[] under the local ids
+  for (size_t u = 0; u < m; u++) nodes[u] = (int32_t)u;
+  const int32_t n_comp = g.scc(nodes, 15, nullptr, 0);
+  // the nontrivial components, numbered by their least txn (the local ids ascend with the txns)
+  std::vector<int32_t> size((size_t)n_comp, 0), id((size_t)n_comp, -1);
+  for (int32_t x : nodes) size[(size_t)g.comp[(size_t)x]]++;
+  std::vector<std::vector<int32_t>> members;
+  for (int32_t x : nodes) {
+    const int32_t c = g.comp[(size_t)x];
+    if (size[(size_t)c] < 2) continue;
+    if (id[(size_t)c] < 0) {
+      id[(size_t)c] = (int32_t)members.size();
+      members.emplace_back();
+    }
+    lscc[(size_t)x] = id[(size_t)c];
+    scc[ids[(size_t)x]] = id[(size_t)c];
+    members[(size_t)id[(size_t)c]].push_back(x);
+  }
+  static const int kCt[4] = {LC_AP_WW, LC_AP_WR, LC_AP_RW, LC_AP_RW};
+  static const int kMask[4] = {1, 3, 3, 7};
+  int64_t n_steps = 0, n_cycles = 0;
+  cycle_off[0] = 0;
+  std::vector<lc_ap_step> steps;
+  // scratch of the G-single searches: a member's index in its SCC, the
+  // candidates with their heads, the SCC's predecessor lists
+  std::vector<int32_t> midx(m, -1), q_node, q_heads, pred;
+  std::vector<int64_t> q_head_off, pred_off;
+  for (size_t c = 0; c < members.size(); c++) {
+    const std::vector<int32_t> &mem = members[c];
+    const int32_t tag = (int32_t)c;
+    int32_t cls = -1;
+    steps.clear();
+    for (size_t i = 0; i < mem.size(); i++) midx[(size_t)mem[i]] = (int32_t)i;
+    for (int k = 0; k < 8 && cls < 0; k++) {
+      const int ct = kCt[k & 3], mask = kMask[k & 3] | (k >= 4 ? 8 : 0);
+      g.scc(mem, mask | (1 << ct), lscc.data(), tag);
+      // u's ct out-edges into its own component of mask + ct: cycle_from's opening test
+      auto closes = [&](int32_t u, int32_t to) {
+        return lscc[(size_t)to] == tag && g.comp[(size_t)to] == g.comp[(size_t)u];
+      };
+      if ((k & 3) != 2) {
+        // ct belongs to mask, so the component is one of mask alone: the head
+        // of a closing edge of u reaches u inside it, and the search from u
+        // succeeds as soon as the opening test passes.  cycles_host's loop
+        // stops at the first member whose search succeeds, which is the first
+        // that passes the test; the members before it leave no trace.
+        for (int32_t u : mem) {
+          bool any = false;
+          for (int64_t i = g.out_off[(size_t)u]; i < g.out_off[(size_t)u + 1] && !any; i++)
+            any = g.edges[i].type == ct && closes(u, g.edges[i].to);
+          if (!any) continue;
+          if (g.cycle_from(u, ct, mask, lscc.data(), tag, &steps)) {
+            cls = k;
+            break;
+          }
+        }
+        continue;
+      }
+      // G-single (k 2) and G-single-realtime (k 6): the component is one of
+      // mask + rw, the search walks mask alone, so a candidate may search the
+      // whole component and fail.  Which candidate is the first to succeed is
+      // a ReachProblem over the SCC's members.
+      q_node.clear();
+      q_heads.clear();
+      q_head_off.assign(1, 0);
+      for (int32_t u : mem) {
+        const size_t h0 = q_heads.size();
+        for (int64_t i = g.out_off[(size_t)u]; i < g.out_off[(size_t)u + 1]; i++) {
+          const lc_ap_edge &e = g.edges[i];
+          if (e.type != ct || !closes(u, e.to)) continue;
+          if (q_heads.size() > h0 && q_heads.back() == midx[(size_t)e.to]) continue;  // (one head, two keys)
+          q_heads.push_back(midx[(size_t)e.to]);
+        }
+        if (q_heads.size() == h0) continue;
+        q_node.push_back(midx[(size_t)u]);
+        q_head_off.push_back((int64_t)q_heads.size());
+      }
+      if (q_node.empty()) continue;
+      int64_t first = -2;  // -2: not asked
+      if (mp->hook) {
+        // the predecessors under mask, inside the components of mask + rw (a
+        // path from a head to its source closes a cycle, so it stays in one)
+        pred.clear();
+        pred_off.assign(1, 0);
+        for (int32_t b : mem) {
+          const int64_t np = g.n_pred(b, mask);
+          for (int64_t i = 0; i < np; i++) {
+            int32_t type;
+            int64_t key;
+            const int32_t a = g.pred(b, mask, i, &type, &key);
+            if (a < 0 || lscc[(size_t)a] != tag || g.comp[(size_t)a] != g.comp[(size_t)b]) continue;
+            pred.push_back(midx[(size_t)a]);
+          }
+          pred_off.push_back((int64_t)pred.size());
+        }
+        const double work = (double)q_node.size() * (double)(mem.size() + pred.size());
+        if (work >= (double)mp->min_work) {
+          if ((int64_t)mem.size() > mp->max_nodes) {
+            mp->n_host_fallbacks++;
+          } else {
+            const auto t0 = std::chrono::steady_clock::now();
+            const ReachProblem rp{(int64_t)mem.size(), pred_off.data(), pred.data(),  (int64_t)q_node.size(),
+                                  q_node.data(),       q_head_off.data(), q_heads.data()};
+            int64_t fh = -1;
+            const int rc = mp->hook(rp, &fh);
+            mp->search_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (rc == -E2BIG) {
+              mp->n_host_fallbacks++;
+            } else if (rc) {
+              return rc;
+            } else if (fh < -1 || fh >= (int64_t)q_node.size()) {
+              return -EIO;
+            } else {
+              mp->n_device_searches++;
+              mp->n_device_queries += (int64_t)q_node.size();
+              first = fh;
+            }
+          }
+        }
+      }
+      if (first == -2) {  // the host loop, over the members that pass the opening test
+        for (int32_t qn : q_node)
+          if (g.cycle_from(mem[(size_t)qn], ct, mask, lscc.data(), tag, &steps)) {
+            cls = k;
+            break;
+          }
+      } else if (first >= 0) {
+        if (!g.cycle_from(mem[(size_t)q_node[(size_t)first]], ct, mask, lscc.data(), tag, &steps)) return -EIO;
+        cls = k;
+      }
+    }
+    if (cls < 0) cls = LC_AP_G2_ITEM + LC_AP_REALTIME;  // (a nontrivial SCC is cyclic under every edge type)
+    for (int32_t x : mem) {
+      scc_class[ids[(size_t)x]] = cls;
+      midx[(size_t)x] = -1;
+    }
+    s.n_class[cls]++;
+    if (n_cycles < LC_AP_MAX_CYCLES) {
+      for (const lc_ap_step &st : steps) out_steps[n_steps++] = lc_ap_step{ids[(size_t)st.txn], st.type, st.key};
+      cycle_scc[n_cycles] = (int32_t)c;
+      cycle_off[++n_cycles] = n_steps;
+    }
+  }
+  for (int64_t i = n_cycles; i < LC_AP_MAX_CYCLES; i++) {
+    cycle_off[i + 1] = n_steps;
+    cycle_scc[i] = -1;
+  }
+  s.n_scc = (int64_t)members.size();
+  s.n_cycles_returned = n_cycles;
+  *counts = s;
+  return 0;
 }
 
 void no_cycles(int64_t n_txns, int32_t *scc, int32_t *scc_class, int64_t *cycle_off, int32_t *cycle_scc,

@@ -1396,6 +1396,7 @@ void lc_close(lc_ctx *c) {
     release(c->wts);
     release(c->pfs);
     release(c->scs);
+    release(c->cys);
   }
   for (auto &f : c->fxs) lc_fx_close(f.first);
   if (c->fx_all) lc_fx_close(c->fx_all);

@@ -338,4 +338,5 @@ struct lc_ctx {
   lcrt::SideState wts;     // lc_watch_check
   lcrt::SideState pfs;     // lc_perf_stats
   lcrt::SideState scs;     // lc_cycle_screen
+  lcrt::SideState cys;     // lc_cycle_reach
 };

@@ -80,10 +80,11 @@ hipError_t launch_marks(const Ws &w, int b, hipStream_t st);
 
 // screen_dev.cpp, for the checkers' drivers: the screen over txns, unique
 // edges, byc and rt_hi that stand on the device (stream st); *scr receives the
-// summary (h2d_ms 0).  n_txns > 0.  0, -ENOMEM or -EIO.
+// summary (h2d_ms 0) and, where clean == 0 and h_mark is given, h_mark the
+// marks (n_txns words of host memory).  n_txns > 0.  0, -ENOMEM or -EIO.
 int screen_resident(lc_ctx *c, hipStream_t st, const lc_ap_txn *d_txns, int64_t n_txns, int64_t n_ok,
                     const lc_ap_edge *d_edges, int64_t n_edges, const int32_t *d_byc, const int32_t *d_rt_hi,
-                    lc_screen_summary *scr);
+                    lc_screen_summary *scr, int32_t *h_mark = nullptr);
 #endif
 
 }  // namespace lcscreen

@@ -162,10 +162,11 @@ int screen_device(lc_ctx *c, const lc_ap_txn *txns, int64_t n_txns, const lc_ap_
 // The screen for a checker's driver (append_dev.cpp, wr_dev.cpp): the txns,
 // the unique edges and real time's byc and rt_hi stand on the device, on the
 // stream the driver works on; the screen's own arrays are carved from its own
-// arena.  No output array: the driver wants the summary alone.
+// arena.  The driver wants the summary, and the marks (h_mark, host memory,
+// n_txns words) where it restricts the host pass to them (clean == 0).
 int lcscreen::screen_resident(lc_ctx *c, hipStream_t st, const lc_ap_txn *d_txns, int64_t n_txns, int64_t n_ok,
                               const lc_ap_edge *d_edges, int64_t n_edges, const int32_t *d_byc, const int32_t *d_rt_hi,
-                              lc_screen_summary *scr) {
+                              lc_screen_summary *scr, int32_t *h_mark) {
   const auto t0 = std::chrono::steady_clock::now();
   SideState &s = c->scs;
   hipStream_t st0;
@@ -193,6 +194,9 @@ int lcscreen::screen_resident(lc_ctx *c, hipStream_t st, const lc_ap_txn *d_txns
   int lb = 0;
   if (int e = run_rounds(c, w, h, d_temp, temp_bytes, st, scr, &lb)) return e;
   HIP_TRY(c, hipEventRecord(k1, st));
+  // the marks only where the host pass will follow them (no mark is written where the labels gave up)
+  if (h_mark && scr->clean == 0)
+    HIP_TRY(c, hipMemcpyAsync(h_mark, w.mark, sizeof(int32_t) * (size_t)n_txns, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   scr->kernel_ms = elapsed_ms(k0, k1);
   scr->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

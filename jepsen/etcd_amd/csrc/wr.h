@@ -36,9 +36,11 @@ int prepare(const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_
 // scc_class, steps, cycle_off, cycle_scc, and every field of sum but
 // n_edges_raw and the device times.  counts[kCounters] are the read counts
 // and the lost-update versions.
-void graph_and_summary(const lc_wr_txn *txns, int64_t n_txns, const Prep &p, const lc_wr_out *out, int64_t n_keys,
-                       int64_t n_edges, const int64_t *counts, lc_wr_summary *sum,
-                       bool no_scc = false);  // no_scc: the caller knows of no nontrivial SCC, and rule 9 only fills
+// no_scc: the caller knows of no nontrivial SCC, and rule 9 only fills.  mp: rule 9 runs over the marked txns
+// (cycles_host_marked); its error, the hook's, is returned and *sum is then not written.  0 otherwise.
+int graph_and_summary(const lc_wr_txn *txns, int64_t n_txns, const Prep &p, const lc_wr_out *out, int64_t n_keys,
+                      int64_t n_edges, const int64_t *counts, lc_wr_summary *sum,
+                      bool no_scc = false, lcgraph::MarkedPass *mp = nullptr);
 
 #if defined(__HIPCC__)
 // One call's device workspace.

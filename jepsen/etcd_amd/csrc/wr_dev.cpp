@@ -8,6 +8,7 @@
 
 #include "runtime.h"
 #include "screen.h"
+#include "cycles.h"
 #include "wr.h"
 
 using namespace lcrt;
@@ -24,7 +25,9 @@ struct Pinned {
 
 int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops, int64_t n_mops,
               uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum,
-              lc_screen_summary *scr) {  // scr: null, or lc_wr_check_screened's
+              lc_screen_summary *scr,  // scr: null, or lc_wr_check_screened's
+              lc_cycle_search_summary *srch = nullptr,
+              bool restricted = false) {  // lc_wr_check_restricted: rule 9 over the screen's marks
   const auto t0 = std::chrono::steady_clock::now();
   lcwr::Prep p;
   const char *why = nullptr;
@@ -33,8 +36,10 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
     return -EINVAL;
   }
   if (n_txns == 0) {
-    if (scr) *scr = lcscreen::empty_summary();
-    return lc_wr_check_host(txns, n_txns, mops, n_mops, flags, out, sum);
+    const int e = lc_wr_check_host(txns, n_txns, mops, n_mops, flags, out, sum);
+    if (!e && scr) *scr = lcscreen::empty_summary();
+    if (!e && srch) *srch = lccyc::search_summary(nullptr);
+    return e;
   }
   lc_wr_limit_info lim;
   lc_wr_limits(&lim);
@@ -235,8 +240,10 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
   }
   // the screen, on the edges and ranges where they stand: a clean graph spares rule 9
   lc_screen_summary scs{};
+  std::vector<int32_t> mark(restricted ? nt : 0);
   if (scr)
-    if (int e = lcscreen::screen_resident(c, st, w.txns, n_txns, p.n_ok, d_edges_b, n_edges, rt.byc, rt.rt_hi, &scs))
+    if (int e = lcscreen::screen_resident(c, st, w.txns, n_txns, p.n_ok, d_edges_b, n_edges, rt.byc, rt.rt_hi, &scs,
+                                          restricted ? mark.data() : nullptr))
       return e;
   if (nm) HIP_TRY(c, hipMemcpyAsync(out->mop_flags, w.mop_flags, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(out->txn_flags, w.txn_flags, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
@@ -252,7 +259,12 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
   int64_t counts[lcwr::kCounters];
   for (int b = 0; b < lcwr::kCounters; b++) counts[b] = lcwr::sum_counters(h.counters, b);
   lc_wr_summary sm;
-  lcwr::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, counts, &sm, scr && scs.clean == 1);
+  // not proved clean, and neither phase gave up: every member of an SCC is marked
+  lcgraph::MarkedPass mp, *marked = restricted && scs.clean == 0 ? &mp : nullptr;
+  if (marked) lccyc::device_pass(c, mark.data(), marked);
+  if (int e = lcwr::graph_and_summary(txns, n_txns, p, out, n_keys, n_edges, counts, &sm, scr && scs.clean == 1,
+                                      marked))
+    return e;
   sm.n_edges_raw = n_sel;
   sm.h2d_ms = elapsed_ms(e0, e1);
   sm.kernel_ms = elapsed_ms(k0, k1);
@@ -260,6 +272,7 @@ int wr_device(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop 
   sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (sum) *sum = sm;
   if (scr) *scr = scs;
+  if (srch) *srch = lccyc::search_summary(marked);
   return 0;
 }
 
@@ -279,5 +292,15 @@ extern "C" int lc_wr_check_screened(lc_ctx *c, const lc_wr_txn *txns, int64_t n_
   lc_screen_summary local;
   return no_bad_alloc(c, "lc_wr_check_screened", [&] {
     return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum, scr ? scr : &local);
+  });
+}
+
+extern "C" int lc_wr_check_restricted(lc_ctx *c, const lc_wr_txn *txns, int64_t n_txns, const lc_wr_mop *mops,
+                                      int64_t n_mops, uint32_t flags, const lc_wr_out *out, lc_wr_summary *sum,
+                                      lc_screen_summary *scr, lc_cycle_search_summary *srch) {
+  if (!c) return -EINVAL;
+  lc_screen_summary local;
+  return no_bad_alloc(c, "lc_wr_check_restricted", [&] {
+    return wr_device(c, txns, n_txns, mops, n_mops, flags, out, sum, scr ? scr : &local, srch, true);
   });
 }

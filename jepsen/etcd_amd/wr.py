@@ -255,12 +255,21 @@ class WrChecker:
     sub-map (clean, rounds, members, ms); every other key is unchanged.  With
     a library that lacks the call the unscreened one runs and the sub-map is
     absent.  Off by default.
+
+    device_cycles=True (it implies device_scc) uses lc_wr_check_restricted
+    (include/lincheck_cycles.h): where the screen does not prove the graph
+    clean, the host pass covers the marked txns only and asks the device which
+    txn closes a G-single cycle; the result map gains a "cycle-search" sub-map
+    beside "scc-screen", every other key is unchanged.  With a library that
+    lacks the call it degrades to device_scc.  Off by default.
     """
 
-    def __init__(self, device_mask=0, device=True, wfr_keys=True, device_scc=False):
+    def __init__(self, device_mask=0, device=True, wfr_keys=True, device_scc=False, device_cycles=False):
         self.device_mask = device_mask
         self.device = device
-        self.device_scc = device_scc
+        self.device_scc = device_scc or device_cycles
+        self.device_cycles = device_cycles
+        self.last_search = None   # device_cycles: lc_cycle_search_summary of the last check, as a dict
         self.last_screen = None   # device_scc: the screen's lc_screen_summary of the last check, as a dict
         self.wfr_keys = wfr_keys
         self._ctx = None
@@ -281,14 +290,16 @@ class WrChecker:
         history = list(history)
         enc = encode(history)
         if self.device:
-            scr = None
-            if self.device_scc and abi.has_screened():
+            scr = srch = None
+            if self.device_cycles and abi.has_restricted():
+                out, s, scr, srch = self._context().wr_check_restricted(enc.txns, enc.mops, self.wfr_keys)
+            elif self.device_scc and abi.has_screened():
                 out, s, scr = self._context().wr_check_screened(enc.txns, enc.mops, self.wfr_keys)
             else:  # (a library without the screened call: the unscreened one, and no sub-map)
                 out, s = self._context().wr_check(enc.txns, enc.mops, self.wfr_keys)
-            self.last_screen = scr
+            self.last_screen, self.last_search = scr, srch
         else:
-            self.last_screen = None
+            self.last_screen = self.last_search = None
             out, s = abi.wr_check_host(enc.txns, enc.mops, self.wfr_keys)
         self.last_out, self.last_summary = out, s
         result = result_map(history, enc, out, s, self.wfr_keys)
@@ -299,6 +310,12 @@ class WrChecker:
                                     "max-rounds": scr["max_rounds"], "rt-members": scr["n_rt_members"],
                                     "trim-survivors": scr["n_trim_survivors"], "kernel-ms": scr["kernel_ms"],
                                     "ms": scr["total_ms"]}
+        if self.device and self.last_search is not None:
+            srch = self.last_search
+            result["cycle-search"] = {"restricted": bool(srch["restricted"]), "marked": srch["n_marked"],
+                                      "device-searches": srch["n_device_searches"],
+                                      "device-queries": srch["n_device_queries"],
+                                      "host-fallbacks": srch["n_host_fallbacks"], "search-ms": srch["search_ms"]}
         return result
 
 
