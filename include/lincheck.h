@@ -577,6 +577,8 @@ const char *lc_build_id(void);
 #include "lincheck_append.h"
 /* lc_wr_check: Elle's rw-register checker (the :wr workload) on the device */
 #include "lincheck_wr.h"
+/* lc_wr_check_lin: the same with Elle's :linearizable-keys? inference */
+#include "lincheck_wrlin.h"
 /* lc_watch_check: the :watch workload's log-convergence checker on the device */
 #include "lincheck_watch.h"
 /* lc_perf_stats: the composed checker's :stats and :perf keys on the device */

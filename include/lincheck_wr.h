@@ -12,9 +12,9 @@
  * The rules below are a re-derivation of elle.rw-register (elle 0.2.x, as
  * jepsen.tests.cycle.wr calls it).  They are this feature's specification;
  * parity with Elle itself is unpinned.  Elle's
- * :sequential-keys? and :linearizable-keys? inferences are out of scope (the
- * workload this stands for leaves the first unset and comments the second out
- * as expensive).
+ * :linearizable-keys? inference is lc_wr_check_lin's (lincheck_wrlin.h: a
+ * call of its own, these calls take no flag for it); :sequential-keys? is out
+ * of scope (the workload this stands for leaves it unset).
  *
  * Positions are history positions, below 2^31 - 1.  Only client ops with
  * :f :txn matter.  Keys and values are int64 (the binding interns anything

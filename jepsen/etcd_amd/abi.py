@@ -283,6 +283,21 @@ class LcWrLimits(ctypes.Structure):
                 ("max_position", ctypes.c_int64), ("max_mops", ctypes.c_int64)]
 
 
+# lc_wr_check_lin (include/lincheck_wrlin.h)
+LC_WR_LINEARIZABLE_KEYS = 2
+WR_LIN_KEY_DTYPE = np.dtype([("n_pairs", "<i8"), ("n_touches", "<i4"), ("n_vedges", "<i4")])
+assert WR_LIN_KEY_DTYPE.itemsize == 16
+
+
+class LcWrLinSummary(ctypes.Structure):
+    _fields_ = [("n_touches", ctypes.c_int64), ("n_pairs", ctypes.c_int64), ("n_vedges", ctypes.c_int64),
+                ("max_key_versions", ctypes.c_int64), ("lin_kernel_ms", ctypes.c_double)]
+
+
+class LcWrLinLimits(ctypes.Structure):
+    _fields_ = [("max_key_versions", ctypes.c_int64), ("wave_key_versions", ctypes.c_int64)]
+
+
 # lc_cycle_screen (include/lincheck_screen.h): the txn and edge records are
 # list-append's
 LC_SCREEN_RT, LC_SCREEN_TRIM = 1, 2
@@ -543,6 +558,15 @@ def lib():
             L.lc_wr_check.restype = ctypes.c_int
             L.lc_wr_limits.argtypes = [ctypes.POINTER(LcWrLimits)]
             L.lc_wr_limits.restype = ctypes.c_int
+        if hasattr(L, "lc_wr_check_lin"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
+            wl = [p, i64, p, i64, ctypes.c_uint32, ctypes.POINTER(LcWrOut), ctypes.POINTER(LcWrSummary), p,
+                  ctypes.POINTER(LcWrLinSummary)]
+            L.lc_wr_check_lin_host.argtypes = wl
+            L.lc_wr_check_lin_host.restype = ctypes.c_int
+            L.lc_wr_check_lin.argtypes = [vp] + wl
+            L.lc_wr_check_lin.restype = ctypes.c_int
+            L.lc_wr_lin_limits.argtypes = [ctypes.POINTER(LcWrLinLimits)]
+            L.lc_wr_lin_limits.restype = ctypes.c_int
         if hasattr(L, "lc_watch_check"):  # (additive to ABI 5: a LINCHECK_LIB may lack it)
             wt = [p, i64, p, i64, i64, ctypes.c_uint32, ctypes.POINTER(LcWtOut), ctypes.POINTER(LcWtSummary)]
             L.lc_watch_check_host.argtypes = wt
@@ -877,6 +901,60 @@ def wr_limits():
     if rc != 0:
         raise LcError(rc, "lc_wr_limits")
     return {f: getattr(s, f) for f, _ in LcWrLimits._fields_}
+
+
+class _WrLinCall(_WrCall):
+    """One lc_wr_check_lin(_host) call's arrays: _WrCall's, the flags with the
+    lin bit, and the lc_wr_lin_key records and the lin summary beside them."""
+
+    def __init__(self, txns, mops, wfr_keys=True, linearizable_keys=True, edge_cap=None):
+        super().__init__(txns, mops, wfr_keys, edge_cap)
+        if linearizable_keys:
+            self.flags |= LC_WR_LINEARIZABLE_KEYS
+        self.lin_keys = np.zeros(max(len(self.mops), 1), dtype=WR_LIN_KEY_DTYPE)
+        self.lin_summary = LcWrLinSummary()
+
+    def args(self):
+        return super().args() + (_ptr(self.lin_keys), ctypes.byref(self.lin_summary))
+
+    def result(self):
+        """-> (the output arrays with "lin_keys" among them, the summary, the lin summary)."""
+        out, s = super().result()
+        out["lin_keys"] = self.lin_keys[:s["n_keys"]]
+        return out, s, _struct_dict(self.lin_summary)
+
+
+def _wr_lin_run(fn, who, error_text, txns, mops, wfr_keys, linearizable_keys, edge_cap):
+    """_wr_run for the lin calls: made again with room after -ENOSPC."""
+    call = _WrLinCall(txns, mops, wfr_keys, linearizable_keys, edge_cap)
+    rc = fn(call)
+    if rc == -28 and edge_cap is None:
+        call = _WrLinCall(call.txns, call.mops, wfr_keys, linearizable_keys, int(call.summary.n_edges))
+        rc = fn(call)
+    if rc != 0:
+        raise LcError(rc, error_text() if rc in (-22, -7, -28) else who)
+    return call.result()
+
+
+def has_wr_lin():
+    """Whether the loaded library has lc_wr_check_lin (a LINCHECK_LIB may lack it)."""
+    return hasattr(lib(), "lc_wr_check_lin")
+
+
+def wr_check_lin_host(txns, mops, wfr_keys=True, linearizable_keys=True, edge_cap=None):
+    """lc_wr_check_lin_host (include/lincheck_wrlin.h) -> (wr_check_host's
+    output arrays and "lin_keys", the summary, the lin summary)."""
+    return _wr_lin_run(lambda call: lib().lc_wr_check_lin_host(*call.args()), "lc_wr_check_lin_host",
+                       lambda: "lc_wr_check_lin_host", txns, mops, wfr_keys, linearizable_keys, edge_cap)
+
+
+def wr_lin_limits():
+    """lc_wr_lin_limits: {"max_key_versions", "wave_key_versions"}."""
+    s = LcWrLinLimits()
+    rc = lib().lc_wr_lin_limits(ctypes.byref(s))
+    if rc != 0:
+        raise LcError(rc, "lc_wr_lin_limits")
+    return _struct_dict(s)
 
 
 def has_screened():
@@ -1423,6 +1501,11 @@ class Context:
         """lc_wr_check: wr_check_host's result, with rules 1-8 on the device."""
         return _wr_run(lambda call: lib().lc_wr_check(self._h, *call.args()), "lc_wr_check", self.last_error,
                        txns, mops, wfr_keys, edge_cap)
+
+    def wr_check_lin(self, txns, mops, wfr_keys=True, linearizable_keys=True, edge_cap=None):
+        """lc_wr_check_lin: wr_check_lin_host's result, with rules 1-8 on the device."""
+        return _wr_lin_run(lambda call: lib().lc_wr_check_lin(self._h, *call.args()), "lc_wr_check_lin",
+                           self.last_error, txns, mops, wfr_keys, linearizable_keys, edge_cap)
 
     def cycle_screen(self, txns, edges):
         """lc_cycle_screen: cycle_screen_host's result, computed on the device."""

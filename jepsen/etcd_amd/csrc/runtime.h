@@ -138,7 +138,7 @@ struct Dev {
 // (the checker's own struct) made by its first call (side_begin);
 // release() frees everything (lc_close).  No device pointer outlives a call
 // but through EvState::w.
-constexpr int kSideEvents = 6;
+constexpr int kSideEvents = 8;  // (lc_wr_check_lin uses two beside lc_wr_check's six)
 struct SideState {
   Buf<char> arena;
   void *pinned = nullptr;

@@ -41,6 +41,7 @@
 
 #include "txngraph_dev.h"
 #include "wr.h"
+#include "wr_lin.h"
 
 namespace lcwr {
 
@@ -300,6 +301,18 @@ hipError_t launch_rules(const Ws &w, int rounds, int32_t *kslots, int64_t *d_n_k
   e = launch_key_slots(w.ktab, w.kcap, kslots, d_n_keys, temp, temp_bytes, st);
   if (e != hipSuccess) return e;
   wr_keys_kernel<<<g_mops, kThreads, 0, st>>>(w, kslots, d_n_keys);
+  return hipGetLastError();
+}
+
+// lc_wr_check_lin (wr_lin.hip) runs the tables' and the records' kernels alone.
+hipError_t launch_tables(const Ws &w, hipStream_t st) {
+  wr_mop_kernel<<<grid_for(w.n_mops, kThreads), kThreads, 0, st>>>(w);
+  wr_txn_kernel<<<grid_for(w.n_txns, kThreads), kThreads, 0, st>>>(w);
+  return hipGetLastError();
+}
+
+hipError_t launch_key_records(const Ws &w, const int32_t *kslots, const int64_t *d_n_keys, hipStream_t st) {
+  wr_keys_kernel<<<grid_for(w.n_mops, kThreads), kThreads, 0, st>>>(w, kslots, d_n_keys);
   return hipGetLastError();
 }
 

@@ -167,10 +167,14 @@ def _read_record(nm, m, name):
     return rec
 
 
-def _step_record(nm, wfr, a, b, typ, k):
+def _step_record(nm, wfr, a, b, typ, k, lin=False):
     if typ == abi.LC_AP_RT:
         return {"type": "realtime", "a-completed": nm.enc.comp[a], "b-invoked": nm.enc.inv[b]}
     rec = {"type": EDGE_NAMES[typ], "key": nm.key(k)}
+    if lin and typ != abi.LC_AP_WR:  # a version edge of any source: which of b's values follows is not restated
+        if typ == abi.LC_AP_RW:
+            rec["value"] = nm.value(nm.ext_read[(a, k)])
+        return rec
     if typ == abi.LC_AP_WR:
         rec["value"] = nm.value(nm.ext_read[(b, k)])
     elif typ == abi.LC_AP_WW:  # a wfr edge: b read a's value and went on to write
@@ -195,7 +199,59 @@ def version_cycle(nm, k, v0):
     return [nm.value(x) for x in reversed(back)]
 
 
-def result_map(history, enc, out, summary, wfr_keys=True):
+def lin_version_edges(nm, k, wfr):
+    """Key k's version edges under include/lincheck_wrlin.h's rule 4', as a
+    dict value -> set of values (ids; LC_WR_NIL is nil), derived from the
+    arrays: initial, wfr (if asked) and lin, the last by walking each touch's
+    later touches in invoke order while none of them has completed before the
+    next is invoked."""
+    enc = nm.enc
+    succ = {}
+    for (k2, v), m in nm.writer.items():
+        if k2 == k and enc.txns["type"][nm.mop_txn[m]] != abi.LC_WR_FAIL:
+            succ.setdefault(abi.LC_WR_NIL, set()).add(v)
+    touches = []  # (inv, comp, first, last), ascending by inv
+    for t in sorted({t for (t, k2) in list(nm.ext_read) + list(nm.writes) if k2 == k}):
+        if enc.txns["type"][t] != abi.LC_WR_OK:
+            continue
+        r, w = nm.ext_read.get((t, k)), nm.writes.get((t, k))
+        first, last = (r if r is not None else w[-1]), (w[-1] if w else r)
+        if wfr and r is not None and w:
+            succ.setdefault(r, set()).add(w[-1])
+        touches.append((int(enc.txns["inv_pos"][t]), int(enc.txns["comp_pos"][t]), first, last))
+    for i, (_, comp, _, last) in enumerate(touches):
+        least = None  # the least completion among the touches invoked after comp, so far
+        for inv2, comp2, first2, _ in touches[i + 1:]:
+            if inv2 < comp:
+                continue
+            if least is not None and least < inv2:
+                break
+            least = comp2 if least is None else min(least, comp2)
+            if last != first2:
+                succ.setdefault(last, set()).add(first2)
+    return succ
+
+
+def lin_version_cycle(nm, k, v0, wfr):
+    """A cycle of key k's version graph through v0, depth first, as the values
+    in their order, the first repeated at the end."""
+    succ = lin_version_edges(nm, k, wfr)
+    path, stack, seen = [v0], [iter(sorted(succ.get(v0, ())))], set()
+    while stack:
+        v = next(stack[-1], None)
+        if v is None:
+            stack.pop()
+            path.pop()
+        elif v == v0:
+            return [nm.value(x) for x in path + [v0]]
+        elif v not in seen:
+            seen.add(v)
+            path.append(v)
+            stack.append(iter(sorted(succ.get(v, ()))))
+    raise AssertionError("key %r: no version cycle through %r" % (k, v0))
+
+
+def result_map(history, enc, out, summary, wfr_keys=True, lin_keys=False):
     """The Elle-shaped result map from the library's arrays."""
     if summary["valid"] < 0:
         return {"valid?": UNKNOWN, "anomaly-types": ["empty-transaction-graph"],
@@ -208,8 +264,10 @@ def result_map(history, enc, out, summary, wfr_keys=True):
                 anomalies.setdefault(name, []).append(_read_record(nm, int(m), name))
     for k in out["keys"]:
         if k["flags"] & abi.LC_WR_K_CYCLIC:
+            kk, v0 = int(k["key"]), int(k["cyc_value"])
             anomalies.setdefault("cyclic-versions", []).append(
-                {"key": nm.key(int(k["key"])), "cycle": version_cycle(nm, int(k["key"]), int(k["cyc_value"]))})
+                {"key": nm.key(kk), "cycle": lin_version_cycle(nm, kk, v0, wfr_keys) if lin_keys
+                 else version_cycle(nm, kk, v0)})
     if summary["n_lost_update"]:
         groups = {}  # (key, value) -> the txns that read it externally and write the key, in txn order
         for (t, k), v in sorted(nm.ext_read.items()):
@@ -224,7 +282,8 @@ def result_map(history, enc, out, summary, wfr_keys=True):
         name = abi.LC_AP_CLASSES[int(out["scc_class"][txs[0]])]
         anomalies.setdefault(name, []).append({
             "cycle": [nm.op(t) for t in txs] + [nm.op(txs[0])],
-            "steps": [_step_record(nm, wfr_keys, txs[i], txs[(i + 1) % len(txs)], int(s["type"]), int(s["key"]))
+            "steps": [_step_record(nm, wfr_keys, txs[i], txs[(i + 1) % len(txs)], int(s["type"]), int(s["key"]),
+                                   lin_keys)
                       for i, s in enumerate(cyc)]})
     # (SCCs past the first LC_AP_MAX_CYCLES are named and counted, without a cycle)
     for i, n in enumerate(summary["n_class"]):
@@ -262,9 +321,25 @@ class WrChecker:
     txn closes a G-single cycle; the result map gains a "cycle-search" sub-map
     beside "scc-screen", every other key is unchanged.  With a library that
     lacks the call it degrades to device_scc.  Off by default.
+
+    linearizable_keys=True adds Elle's :linearizable-keys? inference
+    (include/lincheck_wrlin.h; the reference comments it out as expensive):
+    real time orders each key's versions, so that a stale read between blind
+    writes is caught.  It uses lc_wr_check_lin (device) or
+    lc_wr_check_lin_host; the library must have them.  The result map gains
+    "linearizable-keys": {"touches", "pairs", "version-edges"}; a ww / rw step
+    record then carries "type" and "key" (and for rw the value read) without
+    "value'", and a cyclic key's "cycle" is found depth first over the key's
+    version edges, which the binding derives for the cyclic keys alone.  Not
+    together with device_scc / device_cycles (ValueError).  Off by default.
     """
 
-    def __init__(self, device_mask=0, device=True, wfr_keys=True, device_scc=False, device_cycles=False):
+    def __init__(self, device_mask=0, device=True, wfr_keys=True, device_scc=False, device_cycles=False,
+                 linearizable_keys=False):
+        if linearizable_keys and (device_scc or device_cycles):
+            raise ValueError("linearizable_keys has no screened or restricted call: not with device_scc / device_cycles")
+        self.linearizable_keys = linearizable_keys
+        self.last_lin = None      # linearizable_keys: lc_wr_lin_summary of the last check, as a dict
         self.device_mask = device_mask
         self.device = device
         self.device_scc = device_scc or device_cycles
@@ -289,6 +364,19 @@ class WrChecker:
     def check(self, test, history, opts=None):
         history = list(history)
         enc = encode(history)
+        if self.linearizable_keys:
+            if not abi.has_wr_lin():
+                raise RuntimeError("the loaded library has no lc_wr_check_lin")
+            self.last_screen = self.last_search = None
+            if self.device:
+                out, s, ls = self._context().wr_check_lin(enc.txns, enc.mops, self.wfr_keys)
+            else:
+                out, s, ls = abi.wr_check_lin_host(enc.txns, enc.mops, self.wfr_keys)
+            self.last_out, self.last_summary, self.last_lin = out, s, ls
+            result = result_map(history, enc, out, s, self.wfr_keys, True)
+            result["linearizable-keys"] = {"touches": ls["n_touches"], "pairs": ls["n_pairs"],
+                                           "version-edges": ls["n_vedges"]}
+            return result
         if self.device:
             scr = srch = None
             if self.device_cycles and abi.has_restricted():
